@@ -1,8 +1,19 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X LSD radix sort (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps, writes its outputs when
+--dump-outputs is given, and prints the result line.  Everything else
+described below (lsb_verify of the last step's result, the extra forms in
+fresh processes, the rocprofv3 --pmc traffic passes, the CPU baseline) runs
+only with --full; --no-verify, --no-extras, --no-traffic and
+--no-cpu-baseline then switch single legs off.
+
+--dump-outputs DIR writes what the last timed step computed: each rank's
+sorted records at a fixed, seeded sample of positions (the input is the
+same for the same arguments, so two builds compare output for output).
 
 A step is one full sort (mySort: 8 local passes of 8-bit digits over 64-bit
 keys) of 2^30 16-byte records per GPU (weak scaling: n = N * 2^30), generated on
@@ -70,6 +81,13 @@ def parse():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--n-per-gpu", type=int, default=1 << 30)
+    ap.add_argument("--full", action="store_true",
+                    help="also verify the last step's result (lsb_verify), time the extra forms, measure the "
+                         "dominant kernel's HBM traffic (rocprofv3 --pmc) and run the CPU baseline; a plain "
+                         "run does none of these")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the last step's sorted records at a fixed, seeded "
+                         "sample of positions as DIR/<name>.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-n", type=int, default=0,
                     help="records the CPU baseline sorts (default: the GPU run's n, capped by host "
@@ -119,7 +137,10 @@ def parse():
                     help="N = 1: run the exchange path anyway, over a world-of-one RCCL communicator that "
                          "carries every record through ncclAllToAllv (LSB_OPT_FORCE_EXCHANGE + "
                          "LSB_OPT_EXCHANGE_SELF); the x16 extra is this with --radix-bits 16")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if not a.full:  # a plain run: the headline only
+        a.no_verify = a.no_extras = a.no_traffic = a.no_cpu_baseline = True
+    return a
 
 
 class Dist:
@@ -476,6 +497,33 @@ def timed_sorts(w, d, a, steps, warmup):
     return d.max(sum(times)), verified, d.max_list(times)
 
 
+DUMP_BLOCKS = 256           # sampled blocks per run (shared among the ranks), plus each rank's first and last
+DUMP_BLOCK_RECORDS = 4096   # contiguous records per block: ~2^20 records, 32 MB of float64 in all
+
+
+def dump_outputs(w, N, path):
+    """--dump-outputs: the sorted records the last timed step left in A (what
+    lsb_copy_out hands a caller), at a fixed sample of positions: per local
+    rank its first and last block and DUMP_BLOCKS / N blocks drawn by a
+    generator seeded with the rank.  Written as float64, which holds each
+    32-bit half of a key and a val (a global index) exactly:
+    rank<r>_pos (global positions), rank<r>_key_hi, rank<r>_key_lo, rank<r>_val."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for r in w.local_ranks:
+        here = w.here(r)
+        cnt = min(DUMP_BLOCK_RECORDS, here)
+        last = here - cnt  # the last block's offset
+        drawn = np.random.default_rng(1000 + r).integers(0, last + 1, size=max(1, DUMP_BLOCKS // N))
+        starts = np.unique(np.concatenate([[0, last], drawn])) if cnt else np.zeros(0, dtype=np.int64)
+        rec = [w.copy_out(r, int(s), cnt) for s in starts]
+        rec = np.concatenate(rec) if rec else np.empty(0, dtype=lsbsort.ELEM_DTYPE)
+        pos = (r * w.per + starts[:, None] + np.arange(cnt)[None, :]).reshape(-1)
+        for name, arr in (("pos", pos), ("key_hi", rec["key"] >> np.uint64(32)),
+                          ("key_lo", rec["key"] & np.uint64(0xFFFFFFFF)), ("val", rec["val"])):
+            np.save(os.path.join(path, f"rank{r}_{name}.npy"), arr.astype(np.float64))
+
+
 def free_port():
     import socket
     with socket.socket() as sk:
@@ -554,11 +602,27 @@ def last_json(text):
     return json.loads(lines[-1]) if lines else None
 
 
+def own_argv():
+    """This run's command line without --dump-outputs: an extra form must not
+    write over the headline's outputs."""
+    out, skip = [], False
+    for arg in sys.argv[1:]:
+        opt, eq, _ = arg.partition("=")
+        if skip:
+            skip = False
+        elif opt.startswith("--du") and "--dump-outputs".startswith(opt):  # argparse takes prefixes
+            skip = not eq
+        else:
+            out.append(arg)
+    return out
+
+
 def extra_argv(a, flags, steps=3):
-    """The command line of an extra form: this run's flags plus `flags`,
-    fewer steps, no extras or CPU baseline of its own."""
-    return sys.argv[1:] + flags + ["--steps", str(min(a.steps, steps)), "--warmup", "1",
-                                   "--no-cpu-baseline", "--no-extras", "--no-traffic"]
+    """The command line of an extra form: this run's flags (--full among
+    them, so the form is verified) plus `flags`, fewer steps, no extras or
+    CPU baseline of its own."""
+    return own_argv() + flags + ["--steps", str(min(a.steps, steps)), "--warmup", "1",
+                                 "--no-cpu-baseline", "--no-extras", "--no-traffic"]
 
 
 def whole_key_argv(a):
@@ -891,6 +955,8 @@ def main():
     kernel = "k_scatter" if a.passes == "reduce-scan" else "k_onesweep"
 
     total, verified, step_s = timed_sorts(w, d, a, a.steps, a.warmup)
+    if a.dump_outputs:
+        dump_outputs(w, N, a.dump_outputs)
     stats = w.kernel_stats()
     passes = w.pass_stats()
     scatter_elems = w.scatter_elems()
@@ -940,7 +1006,7 @@ def main():
         if N == 1 and not a.no_traffic:
             traffic, traffic_src = measure_traffic(a, kernel, elems_per_launch)
         elif a.no_traffic:
-            traffic_src = "skipped (--no-traffic)"
+            traffic_src = "skipped (measured with --full, unless --no-traffic)"
         roof = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                 "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
                 "traffic_ratio": round(traffic / (SCATTER_BYTES_PER_ELEM * elems_per_launch), 4)

@@ -48,8 +48,35 @@ def _line(stdout):
     return json.loads(lines[0])
 
 
+def test_plain_run_has_no_extras():
+    """Without --full the line is the headline alone: no extra form runs
+    (each would be its own process), at N = 1 or N > 1."""
+    for args in (["--dry-rank"], ["--gpus", "2", "--dry-rank"]):
+        r = _bench(args + ["--steps", "2"])
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = _line(r.stdout)
+        assert out["ms_per_step"] == 1.0 and out["value"] > 0
+        assert not [k for k in out if k.startswith(("hybrid_", "x16_", "whole_key_", "peer_", "chunked_"))]
+
+
+def test_extras_do_not_take_the_dump_directory(monkeypatch):
+    """An extra form's command line is this run's without --dump-outputs (in
+    any spelling argparse takes), so it cannot write over the headline's
+    outputs; --full stays, so the extra is verified."""
+    for spelled in (["--dump-outputs", "d"], ["--dump-outputs=d"], ["--dump", "d"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--steps", "4"] + spelled + ["--dist", "zipf"])
+        assert bench.own_argv() == ["--full", "--steps", "4", "--dist", "zipf"]
+        a = bench.parse()
+        assert a.dump_outputs == "d" and a.full and not a.no_verify
+        argv = bench.extra_argv(a, ["--passes", "hybrid"])
+        assert argv[:7] == ["--full", "--steps", "4", "--dist", "zipf", "--passes", "hybrid"] and "d" not in argv
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "4"])
+    a = bench.parse()  # a plain run: every other leg off
+    assert a.no_verify and a.no_extras and a.no_traffic and a.no_cpu_baseline and bench.extras_at(a, 1) == []
+
+
 def test_self_launch_relays_rank0_line():
-    r = _bench(["--gpus", "3", "--dry-rank", "--no-cpu-baseline"])
+    r = _bench(["--gpus", "3", "--dry-rank", "--full", "--no-cpu-baseline"])
     assert r.returncode == 0, r.stderr[-3000:]
     out = _line(r.stdout)
     assert out["n_gpus"] == 3 and out["max_rank"] == 2.0  # all three ranks joined one group
@@ -87,7 +114,7 @@ def test_exchange_roofline_keys():
 
 
 def test_peer_failure_keeps_the_headline():
-    r = _bench(["--gpus", "2", "--dry-rank", "--dry-fail-peer", "1", "--no-cpu-baseline"])
+    r = _bench(["--gpus", "2", "--dry-rank", "--full", "--dry-fail-peer", "1", "--no-cpu-baseline"])
     assert r.returncode == 0, r.stderr[-3000:]
     out = _line(r.stdout)
     assert out["value"] == 2 * 16 and out["whole_key_melem_s"] == 2 * 64
@@ -102,7 +129,7 @@ def test_self_launch_fails_with_the_failing_rank():
 
 
 def test_whole_key_failure_keeps_the_headline():
-    r = _bench(["--gpus", "2", "--dry-rank", "--dry-fail-whole-key", "0", "--no-cpu-baseline"])
+    r = _bench(["--gpus", "2", "--dry-rank", "--full", "--dry-fail-whole-key", "0", "--no-cpu-baseline"])
     assert r.returncode == 0, r.stderr[-3000:]
     out = _line(r.stdout)
     assert out["value"] == 2 * 16 and "whole_key_melem_s" not in out
@@ -119,7 +146,7 @@ def test_torchrun_ranks_run_the_extra_in_child_processes(fail_extra):
     import subprocess
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--dry-rank", "--no-cpu-baseline"]
+           "--gpus", "2", "--dry-rank", "--full", "--no-cpu-baseline"]
     if fail_extra:
         cmd += ["--dry-fail-whole-key", "1"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
@@ -138,7 +165,7 @@ def test_eight_rank_dry_launch():
     through the whole host path: eight rank processes, the all-gathered
     exchange stats of eight ranks (7 peers each), both extras in fresh
     processes, one line from rank 0."""
-    r = _bench(["--gpus", "8", "--dry-rank", "--no-cpu-baseline", "--steps", "2", "--warmup", "1"],
+    r = _bench(["--gpus", "8", "--dry-rank", "--full", "--no-cpu-baseline", "--steps", "2", "--warmup", "1"],
                timeout=420)
     assert r.returncode == 0, r.stderr[-3000:]
     out = _line(r.stdout)
@@ -159,7 +186,7 @@ def test_one_gpu_line_carries_hybrid_x16_and_c5_keys():
     x16, the reference's 16-bit digit (BASELINE configs[4]) with its exchange
     path forced through a world-of-one RCCL communicator (--force-exchange);
     both are priced against SURVEY 8(d)'s C5 denominator (192 B per record)."""
-    r = _bench(["--dry-rank", "--no-cpu-baseline", "--steps", "2"])
+    r = _bench(["--dry-rank", "--full", "--no-cpu-baseline", "--steps", "2"])
     assert r.returncode == 0, r.stderr[-3000:]
     out = _line(r.stdout)
     assert out["n_gpus"] == 1 and out["value"] == 8.0 and out["verified"] is True
@@ -177,7 +204,7 @@ def test_one_gpu_line_carries_hybrid_x16_and_c5_keys():
 
 
 def test_x16_failure_keeps_the_headline():
-    r = _bench(["--dry-rank", "--no-cpu-baseline", "--steps", "2", "--dry-fail-x16", "0"])
+    r = _bench(["--dry-rank", "--full", "--no-cpu-baseline", "--steps", "2", "--dry-fail-x16", "0"])
     assert r.returncode == 0, r.stderr[-3000:]
     out = _line(r.stdout)
     assert out["value"] == 8.0 and out["hybrid_melem_s"] == 8.0
@@ -188,14 +215,15 @@ def test_x16_failure_keeps_the_headline():
 def test_wrong_extra_output_fails_the_run(form):
     """An extra whose output fails lsb_verify fails the run (exit 1), as the
     headline does, but its line is still printed (advisor r04)."""
-    r = _bench(["--dry-rank", "--no-cpu-baseline", "--steps", "2", "--dry-unverified", form])
+    r = _bench(["--dry-rank", "--full", "--no-cpu-baseline", "--steps", "2", "--dry-unverified", form])
     assert r.returncode == 1
     out = _line(r.stdout)
     assert out["verified"] is True and out[f"{form}_verified"] is False
 
 
 def test_wrong_peer_output_fails_the_run():
-    r = _bench(["--gpus", "2", "--dry-rank", "--no-cpu-baseline", "--steps", "2", "--dry-unverified", "peer"])
+    r = _bench(["--gpus", "2", "--dry-rank", "--full", "--no-cpu-baseline", "--steps", "2",
+                "--dry-unverified", "peer"])
     assert r.returncode == 1
     out = _line(r.stdout)
     assert out["verified"] is True and out["peer_verified"] is False and out["whole_key_verified"] is True
@@ -212,7 +240,7 @@ def test_eight_rank_memory_fits_the_device(candidates):
     env.pop("LSB_PLACEMENT_CANDIDATES", None)
     if candidates:
         env["LSB_PLACEMENT_CANDIDATES"] = candidates
-    r = _bench(["--gpus", "8", "--dry-rank", "--no-cpu-baseline", "--steps", "2", "--warmup", "1",
+    r = _bench(["--gpus", "8", "--dry-rank", "--full", "--no-cpu-baseline", "--steps", "2", "--warmup", "1",
                 "--dry-fail-peer", "5", "--no-whole-key"], env=env, timeout=420)
     assert r.returncode == 0, r.stderr[-3000:]
     out = _line(r.stdout)
@@ -228,11 +256,12 @@ def test_chunked_extra_at_n2():
     """N > 1 with 16-bit digits: the chunked exchange (LSB_OPT_EXCHANGE_CHUNKS =
     8) is timed as the chunked_* extra beside the headline, verified like the
     others; a wrong chunked output fails the run."""
-    r = _bench(["--gpus", "2", "--dry-rank", "--no-cpu-baseline", "--steps", "2", "--no-whole-key", "--no-peer"])
+    r = _bench(["--gpus", "2", "--dry-rank", "--full", "--no-cpu-baseline", "--steps", "2", "--no-whole-key",
+                "--no-peer"])
     assert r.returncode == 0, r.stderr[-3000:]
     out = _line(r.stdout)
     assert out["chunked_melem_s"] == 2 * 16 and out["chunked_verified"] is True
-    r = _bench(["--gpus", "2", "--dry-rank", "--no-cpu-baseline", "--steps", "2", "--no-whole-key", "--no-peer",
+    r = _bench(["--gpus", "2", "--dry-rank", "--full", "--no-cpu-baseline", "--steps", "2", "--no-whole-key", "--no-peer",
                 "--dry-unverified", "chunked"])
     assert r.returncode == 1
     assert _line(r.stdout)["chunked_verified"] is False

@@ -4,7 +4,7 @@
 # Steps (each under its own time limit; the first failure ends the call):
 #   tests     the whole -m gpu suite
 #   smoke     __graft_entry__.smoke()
-#   bench     bench.py at N = 1 (live PMC traffic + CPU baseline)
+#   bench     bench.py --full at N = 1 (live PMC traffic + CPU baseline)
 #   n2        bench.py --gpus 2 with no launcher over RCCL's socket transport
 #             (two rank processes on the one GPU: the N > 1 code path, not a speed)
 #   n2big     the same at 2^28 records per rank (the placement probe runs in each rank)
@@ -40,24 +40,24 @@ for s in $RUN; do
         || fail smoke $O/smoke.log
       tail -1 $O/smoke.log ;;
     bench)
-      timeout -k 10 500 python -u bench.py > $O/bench.log 2>&1 || fail bench $O/bench.log
+      timeout -k 10 500 python -u bench.py --full > $O/bench.log 2>&1 || fail bench $O/bench.log
       tail -1 $O/bench.log | cut -c1-400 ;;
     n2)
       timeout -k 10 400 python -u bench.py --gpus 2 --transport rccl-sockets --n-per-gpu 67108864 \
-        --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_n2.log 2>&1 || fail n2 $O/bench_n2.log
+        --steps 2 --warmup 1 --full --no-cpu-baseline > $O/bench_n2.log 2>&1 || fail n2 $O/bench_n2.log
       tail -1 $O/bench_n2.log | cut -c1-400 ;;
     n2big)  # N = 2 at 2^28 records per rank: 4 GiB buffers, so each rank runs the placement probe
       timeout -k 10 400 python -u bench.py --gpus 2 --transport rccl-sockets --n-per-gpu 268435456 \
-        --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_n2big.log 2>&1 || fail n2big $O/bench_n2big.log
+        --steps 2 --warmup 1 --full --no-cpu-baseline > $O/bench_n2big.log 2>&1 || fail n2big $O/bench_n2big.log
       tail -1 $O/bench_n2big.log | cut -c1-400 ;;
     n4zipf)
       timeout -k 10 400 python -u bench.py --gpus 4 --transport rccl-sockets --dist zipf \
-        --n-per-gpu 16777216 --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_n4_zipf.log 2>&1 \
+        --n-per-gpu 16777216 --steps 2 --warmup 1 --full --no-cpu-baseline > $O/bench_n4_zipf.log 2>&1 \
         || fail n4zipf $O/bench_n4_zipf.log
       tail -1 $O/bench_n4_zipf.log | cut -c1-400 ;;
     n8)  # the driver's largest N over RCCL sockets: eight rank processes on the one GPU, both extras
       timeout -k 10 600 python -u bench.py --gpus 8 --transport rccl-sockets --n-per-gpu 4194304 \
-        --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_n8.log 2>&1 || fail n8 $O/bench_n8.log
+        --steps 2 --warmup 1 --full --no-cpu-baseline > $O/bench_n8.log 2>&1 || fail n8 $O/bench_n8.log
       tail -1 $O/bench_n8.log | cut -c1-400 ;;
     table)  # the DESIGN.md §4 table (tools/table_runs.sh)
       TABLE=$TAG/table timeout -k 10 1100 bash tools/table_runs.sh > $O/table_summary.log 2>&1 || fail table $O/table_summary.log
@@ -65,7 +65,7 @@ for s in $RUN; do
     torchrun)
       timeout -k 10 400 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
         --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --transport rccl-sockets \
-        --n-per-gpu 67108864 --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_torchrun_n2.log 2>&1 \
+        --n-per-gpu 67108864 --steps 2 --warmup 1 --full --no-cpu-baseline > $O/bench_torchrun_n2.log 2>&1 \
         || fail torchrun $O/bench_torchrun_n2.log
       grep '^{' $O/bench_torchrun_n2.log | tail -1 | cut -c1-400 ;;
     profile)

@@ -13,7 +13,7 @@ for args in "" "--passes reduce-scan" "--dist zipf" "--radix-bits 16" "--n-per-g
     "--passes hybrid" "--passes hybrid --dist zipf" "--passes hybrid --n-per-gpu 4294967296 --steps 3 --warmup 1" \
     "--force-exchange --radix-bits 16" "--force-exchange --radix-bits 16 --dist zipf"; do
   echo "args: $args" >> $T
-  timeout -k 10 300 python -u bench.py --no-cpu-baseline --no-traffic --no-extras $args >> $T 2>&1 || exit 1
+  timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --no-traffic --no-extras $args >> $T 2>&1 || exit 1
 done
 export T
 python3 - <<'PY'
