@@ -24,11 +24,17 @@
 //      self segment straight out of A at once, slice j of R as soon as it has
 //      arrived, overlapping slice j+1 on the wire; then swap
 //
-// Three transports behind one driver: in-process loopback (device copies
-// standing in for the collectives), one rank per process (RCCL, or the
-// caller's host callbacks), and the opt-in peer stores (shmem_putmem /
-// MPI_Put form).  sort_exchange_onesweep is lsb_sort of these forms with
-// single-read local passes and gathered passes after count-only placements.
+// Three transports: in-process loopback (device copies standing in for the
+// collectives), one rank per process (RCCL, or the caller's host callbacks),
+// and the opt-in peer stores (shmem_putmem / MPI_Put form, exchange_peer).
+// The first two differ in two places only, gather_ranks (step 2) and
+// wire_step (step 4); the drivers around them are shared: exchange_sliced
+// (steps 2-5 as above), exchange_chunked (the high-byte pass chunk by chunk
+// under the wire) and lsb_wholekey.cpp's exchange_merge.  Every driver moves
+// records by a plan checked on the host (plan_fetch, lsb_xgeom.h), one wave
+// (lsb_xgeom.h) per step.  sort_exchange_onesweep is lsb_sort of these forms
+// with single-read local passes and gathered passes after count-only
+// placements.
 #include "lsb_rt.h"
 
 namespace lsb_rt {
@@ -56,10 +62,23 @@ int digit_counts(lsb_ctx* c, Rank& r, int digit, const uint64_t** counts) {
   return LSB_OK;
 }
 
+// counts[i] (nb device words) of every rank into every local rank's gather
+// matrix; the collective (not its loopback stand-in) is timed.
+int gather_counts(lsb_ctx* c, const std::vector<const uint64_t*>& counts) {
+  auto send = [&](Rank& r) { return counts[&r - c->ranks.data()]; };
+  auto recv = [](Rank& r) { return r.gather; };
+  if (c->mode == Mode::kLoopback) return gather_ranks(c, (size_t)c->nb, send, recv);
+  HIP_TRY(hipSetDevice(c->ranks[0].dev));
+  Timer t(c, &c->ranks[0], LSB_K_EXCHANGE);
+  return gather_ranks(c, (size_t)c->nb, send, recv);
+}
+
 // Device plan of rank r from its gathered count matrix (r.gather): the
 // placement table stays on the device; only the 2P send/recv counts come
-// back (RCCL takes host counts).  Call plan_fetch after a stream sync.
-int plan_launch(lsb_ctx* c, Rank& r) {
+// back (RCCL takes host counts).  cshift < 8 (exchange_chunked): the plan in
+// chunk order, and its per-chunk counts come back too.  Call plan_fetch after
+// a stream sync.
+int plan_launch(lsb_ctx* c, Rank& r, int cshift = 8) {
   HIP_TRY(hipSetDevice(r.dev));
   if (r.gather_next && !r.gstart) {
     LSB_TRY(dev_alloc(&r.gstart, (size_t)2 * c->P * c->nb));  // gstart, then gadj
@@ -67,24 +86,23 @@ int plan_launch(lsb_ctx* c, Rank& r) {
   }
   {
     Timer t(c, &r, LSB_K_EXCHANGE);
-    HIP_TRY(lsb::launch_plan(r.gather, c->P, c->nb, r.rank, c->n, r.plan_work, r.plan_total,
-                             r.place, r.plan_counts, r.stream, r.gather_next ? r.gstart : nullptr));
+    HIP_TRY(lsb::launch_plan(r.gather, c->P, c->nb, r.rank, c->n, r.plan_work, r.plan_total, r.place,
+                             r.plan_counts, r.stream, r.gather_next ? r.gstart : nullptr, cshift,
+                             cshift < 8 ? r.ck_counts : nullptr));
   }
   HIP_TRY(hipMemcpyAsync(r.counts_h, r.plan_counts, sizeof(int64_t) * 2 * c->P,
                          hipMemcpyDeviceToHost, r.stream));
+  if (cshift < 8)
+    HIP_TRY(hipMemcpyAsync(r.ck_counts_h, r.ck_counts, sizeof(int64_t) * 2 * c->P * (lsb::kBuckets >> cshift),
+                           hipMemcpyDeviceToHost, r.stream));
   return LSB_OK;
 }
 
-void plan_fetch(lsb_ctx* c, Rank& r) {
-  int64_t sd = 0, rd = 0;
-  for (int q = 0; q < c->P; ++q) {
-    r.send_counts[q] = r.counts_h[q];
-    r.recv_counts[q] = r.counts_h[c->P + q];
-    r.send_displs[q] = sd;
-    r.recv_displs[q] = rd;
-    sd += r.send_counts[q];
-    rd += r.recv_counts[q];
-  }
+// The plan on the host, checked (checked_plan): no record moves by a plan
+// whose counts do not add up to the block.
+int plan_fetch(lsb_ctx* c, Rank& r) {
+  return checked_plan(r.counts_h, c->P, r.here, r.send_counts.data(), r.send_displs.data(),
+                      r.recv_counts.data(), r.recv_displs.data());
 }
 
 
@@ -156,35 +174,50 @@ int ensure_recv(lsb_ctx* c, Rank& r) {
   return alloc_third(c, r);
 }
 
+// The self segment stays where it is unless LSB_OPT_EXCHANGE_SELF sends it
+// through the collective like every other source's.
+bool self_in_r(const lsb_ctx* c) { return c->self_coll && c->mode != Mode::kLoopback; }
+
+// Where the next (gathered) pass will find each tile's records: peers'
+// pieces in R, the rank's own in `own`, chunk k's self_adj[k] records further
+// on than in R (chunk_shift 8: one chunk).
+int gather_desc(lsb_ctx* c, Rank& r, const Elem* own, const int64_t (&self_adj)[lsb::kMaxExchangeChunks],
+                int chunk_shift) {
+  lsb::GatherSrc& g = r.gsrc;
+  g.R = r.R;
+  g.A = own;
+  std::copy(std::begin(self_adj), std::end(self_adj), g.self_adj);
+  g.chunk_shift = chunk_shift;
+  g.place = r.place;
+  g.gstart = r.gstart;
+  g.gadj = r.gstart + (size_t)c->P * c->nb;
+  g.desc = r.gdesc;
+  g.P = c->P;
+  g.nb = c->nb;
+  g.me = r.rank;
+  g.self_in_a = !self_in_r(c);
+  g.a_len = g.r_len = r.cap;
+  HIP_TRY(hipSetDevice(r.dev));
+  Timer t(c, &r, LSB_K_EXCHANGE);
+  HIP_TRY(lsb::launch_gather_desc(g, r.here, r.gdesc, r.stream));
+  return LSB_OK;
+}
+
 // The self segment needs no transfer: place it straight out of A as soon as
 // the plan is on the device (call after the host has the plan).  With
 // LSB_OPT_EXCHANGE_SELF it travels through the collective instead and is
-// placed from R by place_slice like every other source.
+// placed from R by place_wave like every other source.
 int place_self(lsb_ctx* c, Rank& r, int shift) {
   const int me = r.rank;
   if (r.send_counts[me] != r.recv_counts[me])
     return fail(LSB_ERR_STATE, "exchange", "self count mismatch");
   LSB_TRY(ensure_recv(c, r));
-  if (r.gather_next) {  // where the next pass will find each tile's records
-    lsb::GatherSrc& g = r.gsrc;
-    g.R = r.R;
-    g.A = r.A;
-    for (int64_t& a : g.self_adj) a = r.send_displs[me] - r.recv_displs[me];
-    g.chunk_shift = 8;
-    g.place = r.place;
-    g.gstart = r.gstart;
-    g.gadj = r.gstart + (size_t)c->P * c->nb;
-    g.desc = r.gdesc;
-    g.P = c->P;
-    g.nb = c->nb;
-    g.me = me;
-    g.self_in_a = !(c->self_coll && c->mode != Mode::kLoopback);
-    g.a_len = g.r_len = r.cap;
-    HIP_TRY(hipSetDevice(r.dev));
-    Timer t(c, &r, LSB_K_EXCHANGE);
-    HIP_TRY(lsb::launch_gather_desc(g, r.here, r.gdesc, r.stream));
+  if (r.gather_next) {
+    int64_t adj[lsb::kMaxExchangeChunks];
+    std::fill(std::begin(adj), std::end(adj), r.send_displs[me] - r.recv_displs[me]);
+    LSB_TRY(gather_desc(c, r, r.A, adj, 8));
   }
-  if (c->self_coll && c->mode != Mode::kLoopback) return LSB_OK;
+  if (self_in_r(c)) return LSB_OK;
   HIP_TRY(hipSetDevice(r.dev));
   HIP_TRY(hipEventRecord(r.pevent, r.stream));  // plan kernels done
   HIP_TRY(hipStreamWaitEvent(r.pstream, r.pevent, 0));
@@ -192,75 +225,121 @@ int place_self(lsb_ctx* c, Rank& r, int shift) {
                      r.recv_counts[me]);
 }
 
-// Slice j of every peer segment has arrived in R (r.stream): place it on
-// r.pstream while r.stream carries slice j + 1.
-int place_slice(lsb_ctx* c, Rank& r, int shift, int j) {
-  HIP_TRY(hipSetDevice(r.dev));
-  HIP_TRY(hipEventRecord(r.pevent, r.stream));
-  HIP_TRY(hipStreamWaitEvent(r.pstream, r.pevent, 0));
-  const bool self_in_r = c->self_coll && c->mode != Mode::kLoopback;
+// Place a received wave on r.pstream: every source's range of R, and the
+// rank's own records (unless they came through the collective) out of `own`
+// where the wave sends them from; own == nullptr: placed already (place_self).
+int place_wave(lsb_ctx* c, Rank& r, int shift, const Wave& w, const Elem* own) {
   for (int s = 0; s < c->P; ++s) {
-    if (s == r.rank && !self_in_r) continue;
-    const int64_t lo = slice_part(r.recv_counts[s], j, slices_of(c));
-    const int64_t hi = slice_part(r.recv_counts[s], j + 1, slices_of(c));
-    LSB_TRY(place_range(c, r, shift, s, r.R + r.recv_displs[s] + lo, r.recv_displs[s] + lo, hi - lo));
+    const Elem* src = r.R + w.roff[s];
+    if (s == r.rank && !self_in_r(c)) {
+      if (!own) continue;
+      src = own + w.soff[s];
+    }
+    LSB_TRY(place_range(c, r, shift, s, src, w.roff[s], w.rcnt[s]));
   }
   return LSB_OK;
 }
 
-// ---- exchange: in-process loopback --------------------------------------
-// The same slices and placement as the RCCL path; device copies stand in for
-// ncclAllToAllv.
-int exchange_loopback(lsb_ctx* c, int digit) {
-  const int shift = digit * c->bits;
-  const size_t nb = (size_t)c->nb;
-  // counts of every rank into every rank's gather matrix (the device copies
-  // stand in for ncclAllGather), then every rank's device plan.
-  std::vector<const uint64_t*> counts(c->ranks.size(), nullptr);
-  for (Rank& r : c->ranks) LSB_TRY(digit_counts(c, r, digit, &counts[r.rank]));
-  for (Rank& r : c->ranks) {
-    HIP_TRY(hipSetDevice(r.dev));
-    HIP_TRY(hipStreamSynchronize(r.stream));
-  }
-  for (Rank& q : c->ranks) {
-    HIP_TRY(hipSetDevice(q.dev));
-    for (Rank& s : c->ranks)
-      HIP_TRY(hipMemcpyAsync(q.gather + (size_t)s.rank * nb, counts[s.rank], sizeof(uint64_t) * nb,
-                             hipMemcpyDefault, q.stream));
-    LSB_TRY(plan_launch(c, q));
-  }
-  for (Rank& r : c->ranks) {
-    HIP_TRY(hipSetDevice(r.dev));
-    HIP_TRY(hipStreamSynchronize(r.stream));
-    plan_fetch(c, r);
-  }
-  for (Rank& q : c->ranks)
-    for (Rank& s : c->ranks)
-      if (s.send_counts[q.rank] != q.recv_counts[s.rank])
-        return fail(LSB_ERR_STATE, "exchange_loopback", "send/recv count mismatch");
-  for (Rank& r : c->ranks) LSB_TRY(place_self(c, r, shift));
-  // all-to-all-v, slice by slice: part j of segment q of rank s's
-  // digit-ordered A -> rank q's R.
-  for (int j = 0; j < slices_of(c); ++j) {
-    for (Rank& q : c->ranks) {
-      HIP_TRY(hipSetDevice(q.dev));
-      Timer t(c, &q, LSB_K_WIRE);
-      for (Rank& s : c->ranks) {
-        if (s.rank == q.rank) continue;
-        const int64_t cnt = s.send_counts[q.rank];
-        const int64_t lo = slice_part(cnt, j, slices_of(c)), hi = slice_part(cnt, j + 1, slices_of(c));
-        if (hi <= lo) continue;
-        LSB_TRY(copy_range(c, q, q.R + q.recv_displs[s.rank] + lo, s, s.A + s.send_displs[q.rank] + lo, hi - lo,
-                           q.stream));
+// One all-to-all-v step (lsb_rt.h).  Loopback: part q of rank s's source ->
+// rank q's R, after the check the collective's two ends cannot make: that
+// sender and receiver agree on the count.  One rank per process: the
+// collective in uint64 units (ncclAllToAllv; the reference's MPI_Alltoallv,
+// mpi/mpi_lsbsort.cpp:316-324); the own entry is 0 because the own records
+// are used where they lie (unless LSB_OPT_EXCHANGE_SELF sends them too).
+int wire_step(lsb_ctx* c, const std::vector<Wave>& w, const std::vector<Elem*>& src, int64_t bound,
+              hipStream_t Rank::*st) {
+  const int P = c->P;
+  if (c->mode == Mode::kLoopback) {
+    for (int q = 0; q < P; ++q) {
+      Rank& rq = c->ranks[q];
+      HIP_TRY(hipSetDevice(rq.dev));
+      Timer t(c, &rq, LSB_K_WIRE, rq.*st);
+      for (int s = 0; s < P; ++s) {
+        if (s == q) continue;
+        if (w[s].scnt[q] != w[q].rcnt[s]) return fail(LSB_ERR_STATE, "exchange", "send/recv count mismatch");
+        LSB_TRY(copy_range(c, rq, rq.R + w[q].roff[s], c->ranks[s], src[s] + w[s].soff[q], w[q].rcnt[s], rq.*st));
       }
     }
-    for (Rank& q : c->ranks) LSB_TRY(place_slice(c, q, shift, j));
+    return LSB_OK;
   }
-  // Every rank's copies out of A must be done before any rank's next pass
-  // rewrites that A (it becomes B after the swap).
+  Rank& r = c->ranks[0];
+  HIP_TRY(hipSetDevice(r.dev));
+  std::vector<size_t> sc(P), sd(P), rc(P), rd(P);
+  for (int q = 0; q < P; ++q) {
+    const bool skip = q == r.rank && !c->self_coll;
+    sc[q] = skip ? 0 : (size_t)w[0].scnt[q] * 2;
+    rc[q] = skip ? 0 : (size_t)w[0].rcnt[q] * 2;
+    sd[q] = (size_t)w[0].soff[q] * 2;
+    rd[q] = (size_t)w[0].roff[q] * 2;
+  }
+  Timer t(c, &r, LSB_K_WIRE, r.*st);
+  return coll_alltoallv_u64(c, r, reinterpret_cast<const uint64_t*>(src[0]), sc.data(), sd.data(),
+                            reinterpret_cast<uint64_t*>(r.R), rc.data(), rd.data(), (size_t)bound * 2, r.*st);
+}
+
+// How RCCL calls of more than 1 GiB per peer are cut (coll_alltoallv_u64),
+// alike on every rank: by the largest segment of this exchange on any rank
+// (the local ones: send, recv [q * C + k]), one all-reduce of one word, asked
+// only when a block could exceed the bound at all (may_exceed); else by the
+// rank block.
+int call_bound(lsb_ctx* c, const int64_t* send, const int64_t* recv, int C, bool may_exceed, int64_t* seg) {
+  *seg = c->per;
+  if (c->mode != Mode::kRccl || !may_exceed) return LSB_OK;
+  int64_t neg = -max_segment(send, recv, c->P, C, c->self_coll ? -1 : c->ranks[0].rank);
+  LSB_TRY(allreduce_min_i64(c, &neg));
+  *seg = -neg;
+  return LSB_OK;
+}
+
+// Every local rank's counts of the exchange digit into every local rank's
+// gather matrix.
+int gather_digit_counts(lsb_ctx* c, int digit) {
+  std::vector<const uint64_t*> counts(c->ranks.size(), nullptr);
+  for (size_t i = 0; i < c->ranks.size(); ++i) LSB_TRY(digit_counts(c, c->ranks[i], digit, &counts[i]));
+  return gather_counts(c, counts);
+}
+
+// ---- exchange: in slices (loopback, RCCL, the caller's collectives) --------
+int exchange_sliced(lsb_ctx* c, int digit) {
+  const int shift = digit * c->bits, S = slices_of(c);
+  const size_t nr = c->ranks.size();
+  LSB_TRY(gather_digit_counts(c, digit));
+  for (Rank& r : c->ranks) LSB_TRY(plan_launch(c, r));
+  for (Rank& r : c->ranks) {
+    HIP_TRY(hipSetDevice(r.dev));
+    HIP_TRY(hipStreamSynchronize(r.stream));
+    LSB_TRY(plan_fetch(c, r));
+  }
+  for (Rank& r : c->ranks) LSB_TRY(place_self(c, r, shift));
+  const Rank& r0 = c->ranks[0];
+  int64_t seg = 0;
+  LSB_TRY(call_bound(c, r0.send_counts.data(), r0.recv_counts.data(), 1,
+                     (size_t)slice_bound(c->per, 0, S) * 2 > max_call_u64(), &seg));
+  // all-to-all-v out of the digit-ordered A, slice by slice; slice j is
+  // placed on r.pstream while r.stream carries slice j + 1.
+  std::vector<Wave> w(nr);
+  std::vector<Elem*> src(nr);
+  for (size_t i = 0; i < nr; ++i) src[i] = c->ranks[i].A;
+  for (int j = 0; j < S; ++j) {
+    for (size_t i = 0; i < nr; ++i) {
+      const Rank& r = c->ranks[i];
+      slice_wave(c->P, r.send_counts.data(), r.send_displs.data(), r.recv_counts.data(), r.recv_displs.data(), j, S,
+                 w[i]);
+    }
+    LSB_TRY(wire_step(c, w, src, slice_bound(seg, j, S), &Rank::stream));
+    for (size_t i = 0; i < nr; ++i) {
+      Rank& r = c->ranks[i];
+      HIP_TRY(hipSetDevice(r.dev));
+      HIP_TRY(hipEventRecord(r.pevent, r.stream));
+      HIP_TRY(hipStreamWaitEvent(r.pstream, r.pevent, 0));
+      LSB_TRY(place_wave(c, r, shift, w[i], nullptr));
+    }
+  }
+  // Loopback: every rank's copies out of A must be done before any rank's
+  // next pass rewrites that A (it becomes B after the swap).
   for (Rank& r : c->ranks) {
     LSB_TRY(join_place_timed(c, r));
-    HIP_TRY(hipStreamSynchronize(r.stream));
+    if (c->mode == Mode::kLoopback) HIP_TRY(hipStreamSynchronize(r.stream));
     end_placement(r);
   }
   return LSB_OK;
@@ -378,28 +457,7 @@ int exchange_peer(lsb_ctx* c, int digit) {
   const int shift = digit * c->bits;
   const size_t nb = (size_t)c->nb;
   LSB_TRY(peer_setup(c));
-  // counts of every rank into every local rank's gather matrix
-  if (c->mode == Mode::kLoopback) {
-    std::vector<const uint64_t*> counts(c->ranks.size(), nullptr);
-    for (Rank& r : c->ranks) LSB_TRY(digit_counts(c, r, digit, &counts[r.rank]));
-    for (Rank& r : c->ranks) {
-      HIP_TRY(hipSetDevice(r.dev));
-      HIP_TRY(hipStreamSynchronize(r.stream));
-    }
-    for (Rank& q : c->ranks) {
-      HIP_TRY(hipSetDevice(q.dev));
-      for (Rank& s : c->ranks)
-        HIP_TRY(hipMemcpyAsync(q.gather + (size_t)s.rank * nb, counts[s.rank],
-                               sizeof(uint64_t) * nb, hipMemcpyDefault, q.stream));
-    }
-  } else {
-    Rank& r = c->ranks[0];
-    const uint64_t* counts = nullptr;
-    LSB_TRY(digit_counts(c, r, digit, &counts));
-    HIP_TRY(hipSetDevice(r.dev));
-    Timer t(c, &r, LSB_K_EXCHANGE);
-    LSB_TRY(coll_allgather_u64(c, r, counts, r.gather, nb));
-  }
+  LSB_TRY(gather_digit_counts(c, digit));
   for (Rank& r : c->ranks) {
     HIP_TRY(hipSetDevice(r.dev));
     if (!r.peer_base) {
@@ -422,71 +480,10 @@ int exchange_peer(lsb_ctx* c, int digit) {
   return LSB_OK;
 }
 
-// ---- exchange: one rank per process (RCCL, or the caller's collectives) ----
-int exchange_rccl(lsb_ctx* c, int digit) {
-  const int shift = digit * c->bits;
-  const int P = c->P;
-  const size_t nb = (size_t)c->nb;
-  Rank& r = c->ranks[0];
-  const uint64_t* counts = nullptr;
-  LSB_TRY(digit_counts(c, r, digit, &counts));
-  HIP_TRY(hipSetDevice(r.dev));
-  {
-    Timer t(c, &r, LSB_K_EXCHANGE);
-    LSB_TRY(coll_allgather_u64(c, r, counts, r.gather, nb));
-  }
-  LSB_TRY(plan_launch(c, r));
-  HIP_TRY(hipStreamSynchronize(r.stream));
-  plan_fetch(c, r);
-  LSB_TRY(place_self(c, r, shift));
-  const int me = r.rank;
-  // Calls of more than 1 GiB per peer are cut (coll_alltoallv_u64), alike on
-  // every rank: by the largest peer segment of this exchange on any rank, one
-  // all-reduce of one word, asked only when a block could exceed it at all.
-  int64_t seg = c->per;
-  if (c->mode == Mode::kRccl && (size_t)slice_bound(c->per, 0, slices_of(c)) * 2 > max_call_u64()) {
-    int64_t m = 0;
-    for (int q = 0; q < P; ++q)
-      if (q != me || c->self_coll) m = std::max(m, std::max(r.send_counts[q], r.recv_counts[q]));
-    int64_t neg = -m;
-    LSB_TRY(allreduce_min_i64(c, &neg));
-    seg = -neg;
-  }
-  // ncclAllToAllv per slice (the reference's MPI_Alltoallv,
-  // mpi/mpi_lsbsort.cpp:316-324), in uint64 units; the self entry is 0
-  // because the self segment was placed straight out of A (unless
-  // LSB_OPT_EXCHANGE_SELF sends it through the collective too).
-  const bool skip_self = !c->self_coll;
-  std::vector<size_t> sc(P), sd(P), rc(P), rdp(P);
-  for (int j = 0; j < slices_of(c); ++j) {
-    {
-      Timer t(c, &r, LSB_K_WIRE);
-      for (int q = 0; q < P; ++q) {
-        const int64_t slo = slice_part(r.send_counts[q], j, slices_of(c));
-        const int64_t shi = slice_part(r.send_counts[q], j + 1, slices_of(c));
-        const int64_t rlo = slice_part(r.recv_counts[q], j, slices_of(c));
-        const int64_t rhi = slice_part(r.recv_counts[q], j + 1, slices_of(c));
-        sc[q] = q == me && skip_self ? 0 : (size_t)(shi - slo) * 2;
-        rc[q] = q == me && skip_self ? 0 : (size_t)(rhi - rlo) * 2;
-        sd[q] = (size_t)(r.send_displs[q] + slo) * 2;
-        rdp[q] = (size_t)(r.recv_displs[q] + rlo) * 2;
-      }
-      LSB_TRY(coll_alltoallv_u64(c, r, reinterpret_cast<const uint64_t*>(r.A), sc.data(),
-                                 sd.data(), reinterpret_cast<uint64_t*>(r.R), rc.data(),
-                                 rdp.data(), (size_t)slice_bound(seg, j, slices_of(c)) * 2));
-    }
-    LSB_TRY(place_slice(c, r, shift, j));
-  }
-  LSB_TRY(join_place_timed(c, r));
-  end_placement(r);
-  return LSB_OK;
-}
-
 int exchange_digit(lsb_ctx* c, int digit) {
   ++c->xs_exchanges;
   if (c->peer) return exchange_peer(c, digit);
-  if (c->mode != Mode::kLoopback) return exchange_rccl(c, digit);
-  return exchange_loopback(c, digit);
+  return exchange_sliced(c, digit);
 }
 
 // ---- the per-digit exchange in chunks (LSB_OPT_EXCHANGE_CHUNKS) -------------
@@ -523,15 +520,6 @@ namespace {
 
 int cshift_of(int C) { return C >= 8 ? 5 : C == 4 ? 6 : 7; }
 
-// One rank's chunk geometry (host) after the plan.
-struct ChunkGeom {
-  std::vector<int64_t> lo;     // [C + 1] chunk bounds in A and B
-  std::vector<int64_t> send;   // [q * C + k] my records of chunk k for owner q
-  std::vector<int64_t> recv;   // [s * C + k] source s's records of chunk k for me
-  std::vector<int64_t> sdisp;  // [q * C + k] where owner q's share starts inside chunk k
-  std::vector<int64_t> rpre;   // [s * C + k] where chunk k starts inside source s's range of R
-};
-
 int chunk_ensure(lsb_ctx* c, Rank& r) {
   if (r.xstream) return LSB_OK;
   HIP_TRY(hipSetDevice(r.dev));
@@ -548,77 +536,15 @@ int chunk_ensure(lsb_ctx* c, Rank& r) {
   return LSB_OK;
 }
 
-// The plan in chunk order; the send / recv totals and the per-chunk counts
-// come back to the host (after a stream sync: chunk_geom).
-int chunk_plan(lsb_ctx* c, Rank& r, int cs) {
-  HIP_TRY(hipSetDevice(r.dev));
-  if (r.gather_next && !r.gstart) {
-    LSB_TRY(dev_alloc(&r.gstart, (size_t)2 * c->P * c->nb));  // gstart, then gadj
-    LSB_TRY(dev_alloc(&r.gdesc, (size_t)lsb::onesweep_tiles(r.here)));
-  }
-  const int C = lsb::kBuckets >> cs;
-  {
-    Timer t(c, &r, LSB_K_EXCHANGE);
-    HIP_TRY(lsb::launch_plan(r.gather, c->P, c->nb, r.rank, c->n, r.plan_work, r.plan_total, r.place,
-                             r.plan_counts, r.stream, r.gather_next ? r.gstart : nullptr, cs, r.ck_counts));
-  }
-  HIP_TRY(hipMemcpyAsync(r.counts_h, r.plan_counts, sizeof(int64_t) * 2 * c->P, hipMemcpyDeviceToHost, r.stream));
-  HIP_TRY(hipMemcpyAsync(r.ck_counts_h, r.ck_counts, sizeof(int64_t) * 2 * c->P * C, hipMemcpyDeviceToHost,
-                         r.stream));
-  return LSB_OK;
-}
-
-int chunk_geom(lsb_ctx* c, Rank& r, int C, ChunkGeom& g) {
-  const int P = c->P, lw = lsb::kBuckets / C;
-  g.lo.assign(C + 1, 0);
-  if (r.here > 0) {
-    int64_t acc = 0;
-    for (int l = 0; l < lsb::kBuckets; ++l) {
-      if (l % lw == 0) g.lo[l / lw] = acc;
-      for (int x = 0; x < lsb::kOnesweepSubs; ++x) acc += r.lo_hist_h[x * lsb::kBuckets + l];
-    }
-    g.lo[C] = acc;
-    if (acc != r.here) return fail(LSB_ERR_STATE, "exchange_chunked", "chunk bounds do not cover the block");
-  }
-  g.send.assign((size_t)P * C, 0);
-  g.recv.assign((size_t)P * C, 0);
-  g.sdisp.assign((size_t)P * C, 0);
-  g.rpre.assign((size_t)P * C, 0);
-  for (int i = 0; i < P * C; ++i) {
-    g.send[i] = r.ck_counts_h[i];
-    g.recv[i] = r.ck_counts_h[(size_t)P * C + i];
-  }
-  for (int k = 0; k < C; ++k) {
-    int64_t a = 0;
-    for (int q = 0; q < P; ++q) {
-      g.sdisp[(size_t)q * C + k] = a;
-      a += g.send[(size_t)q * C + k];
-    }
-    if (a != g.lo[k + 1] - g.lo[k]) return fail(LSB_ERR_STATE, "exchange_chunked", "chunk send counts");
-  }
-  for (int q = 0; q < P; ++q) {
-    int64_t a = 0, sa = 0;
-    for (int k = 0; k < C; ++k) {
-      g.rpre[(size_t)q * C + k] = a;
-      a += g.recv[(size_t)q * C + k];
-      sa += g.send[(size_t)q * C + k];
-    }
-    if (a != r.recv_counts[q] || sa != r.send_counts[q])
-      return fail(LSB_ERR_STATE, "exchange_chunked", "chunk counts do not add up");
-  }
-  return LSB_OK;
-}
-
 }  // namespace
 
 int exchange_chunked(lsb_ctx* c, int digit, const std::vector<const uint32_t*>& lo_hist) {
   ++c->xs_exchanges;
   const int C = std::min(c->xchunks, lsb::kMaxExchangeChunks), cs = cshift_of(C), P = c->P;
-  const size_t nb = (size_t)c->nb;
   const int shift = digit * 16, hi_shift = shift + lsb::kDigitBits;
-  const bool loop = c->mode == Mode::kLoopback;
   const size_t nr = c->ranks.size();
   std::vector<ChunkGeom> geo(nr);
+  std::vector<Wave> w(nr);
   std::vector<Elem*> X(nr), Y(nr);  // the high-byte pass reads X (A, sorted by l) and writes Y (B)
   // 1. the count read
   for (size_t i = 0; i < nr; ++i) {
@@ -637,84 +563,33 @@ int exchange_chunked(lsb_ctx* c, int digit, const std::vector<const uint32_t*>& 
                            hipMemcpyDeviceToHost, r.stream));
   }
   // 2. the counts to every rank, the plan in chunk order
-  if (loop) {
-    for (Rank& r : c->ranks) {
-      HIP_TRY(hipSetDevice(r.dev));
-      HIP_TRY(hipStreamSynchronize(r.stream));
-    }
-    for (Rank& q : c->ranks) {
-      HIP_TRY(hipSetDevice(q.dev));
-      for (Rank& s : c->ranks)
-        HIP_TRY(hipMemcpyAsync(q.gather + (size_t)s.rank * nb, s.totals16, sizeof(uint64_t) * nb, hipMemcpyDefault,
-                               q.stream));
-      LSB_TRY(chunk_plan(c, q, cs));
-    }
-  } else {
-    Rank& r = c->ranks[0];
-    {
-      Timer t(c, &r, LSB_K_EXCHANGE);
-      LSB_TRY(coll_allgather_u64(c, r, r.totals16, r.gather, nb));
-    }
-    LSB_TRY(chunk_plan(c, r, cs));
-  }
+  std::vector<const uint64_t*> counts(nr);
+  for (size_t i = 0; i < nr; ++i) counts[i] = c->ranks[i].totals16;
+  LSB_TRY(gather_counts(c, counts));
+  for (Rank& r : c->ranks) LSB_TRY(plan_launch(c, r, cs));
   for (size_t i = 0; i < nr; ++i) {
     Rank& r = c->ranks[i];
     HIP_TRY(hipSetDevice(r.dev));
     HIP_TRY(hipStreamSynchronize(r.stream));
-    plan_fetch(c, r);
-    LSB_TRY(chunk_geom(c, r, C, geo[i]));
+    LSB_TRY(plan_fetch(c, r));
+    LSB_TRY(chunk_geom(P, C, r.here, r.lo_hist_h, lsb::kBuckets, lsb::kOnesweepSubs, r.ck_counts_h,
+                       r.send_counts.data(), r.recv_counts.data(), geo[i]));
   }
-  if (loop)
-    for (size_t q = 0; q < nr; ++q)
-      for (size_t s = 0; s < nr; ++s)
-        for (int k = 0; k < C; ++k)
-          if (geo[s].send[q * C + k] != geo[q].recv[s * C + k])
-            return fail(LSB_ERR_STATE, "exchange_chunked", "send/recv count mismatch");
-  const bool self_in_r = c->self_coll && !loop;
   // Where the next (gathered) pass finds each tile's records: peers' pieces
   // in R, my own in Y, chunk k's at its own offset.
   for (size_t i = 0; i < nr; ++i) {
     Rank& r = c->ranks[i];
-    const int me = r.rank;
     if (!r.gather_next) continue;
-    lsb::GatherSrc& g = r.gsrc;
-    g.R = r.R;
-    g.A = Y[i];
-    for (int k = 0; k < lsb::kMaxExchangeChunks; ++k)
-      g.self_adj[k] = k < C ? geo[i].lo[k] + geo[i].sdisp[(size_t)me * C + k] -
-                                  (r.recv_displs[me] + geo[i].rpre[(size_t)me * C + k])
-                            : 0;
-    g.chunk_shift = cs;
-    g.place = r.place;
-    g.gstart = r.gstart;
-    g.gadj = r.gstart + (size_t)P * nb;
-    g.desc = r.gdesc;
-    g.P = P;
-    g.nb = c->nb;
-    g.me = me;
-    g.self_in_a = !self_in_r;
-    g.a_len = g.r_len = r.cap;
-    HIP_TRY(hipSetDevice(r.dev));
-    Timer t(c, &r, LSB_K_EXCHANGE);
-    HIP_TRY(lsb::launch_gather_desc(g, r.here, r.gdesc, r.stream));
-  }
-  // RCCL calls of more than 1 GiB per peer are cut alike on every rank
-  // (coll_alltoallv_u64): the largest (peer, chunk) segment anywhere.
-  int64_t seg = 0;
-  if (!loop) {
-    Rank& r = c->ranks[0];
-    for (int q = 0; q < P; ++q)
-      if (q != r.rank || c->self_coll)
-        for (int k = 0; k < C; ++k)
-          seg = std::max(seg, std::max(geo[0].send[(size_t)q * C + k], geo[0].recv[(size_t)q * C + k]));
-    if (c->mode == Mode::kRccl && (size_t)c->per * 2 > max_call_u64()) {  // a chunk may hold the block
-      int64_t neg = -seg;
-      LSB_TRY(allreduce_min_i64(c, &neg));
-      seg = -neg;
-    } else {
-      seg = c->per;
+    int64_t adj[lsb::kMaxExchangeChunks] = {};
+    for (int k = 0; k < C; ++k) {
+      chunk_wave(P, C, geo[i], r.recv_displs.data(), k, w[i]);
+      adj[k] = w[i].soff[r.rank] - w[i].roff[r.rank];
     }
+    LSB_TRY(gather_desc(c, r, Y[i], adj, cs));
   }
+  int64_t seg = 0;
+  LSB_TRY(call_bound(c, geo[0].send.data(), geo[0].recv.data(), C,
+                     (size_t)c->per * 2 > max_call_u64() /* a chunk may hold the block */, &seg));
   // 3. chunk by chunk: the high-byte pass, then the wire
   for (int k = 0; k < C; ++k) {
     for (size_t i = 0; i < nr; ++i) {
@@ -747,43 +622,16 @@ int exchange_chunked(lsb_ctx* c, int digit, const std::vector<const uint32_t*>& 
       }
       HIP_TRY(hipEventRecord(r.ck_hi[k], r.stream));
     }
-    if (loop) {
-      for (size_t q = 0; q < nr; ++q) {
-        Rank& rq = c->ranks[q];
-        HIP_TRY(hipSetDevice(rq.dev));
-        for (size_t s = 0; s < nr; ++s) HIP_TRY(hipStreamWaitEvent(rq.xstream, c->ranks[s].ck_hi[k], 0));
-        {
-          Timer t(c, &rq, LSB_K_WIRE, rq.xstream);
-          for (size_t s = 0; s < nr; ++s) {
-            if (s == q) continue;
-            const int64_t cnt = geo[q].recv[s * C + k];
-            if (cnt <= 0) continue;
-            const Elem* src = Y[s] + geo[s].lo[k] + geo[s].sdisp[q * C + k];
-            LSB_TRY(copy_range(c, rq, rq.R + rq.recv_displs[s] + geo[q].rpre[s * C + k], c->ranks[s], src, cnt,
-                               rq.xstream));
-          }
-        }
-        HIP_TRY(hipEventRecord(rq.ck_wire[k], rq.xstream));
-      }
-    } else {
-      Rank& r = c->ranks[0];
-      const ChunkGeom& g = geo[0];
-      const int me = r.rank;
-      HIP_TRY(hipStreamWaitEvent(r.xstream, r.ck_hi[k], 0));
-      std::vector<size_t> sc(P), sd(P), rc(P), rdp(P);
-      for (int q = 0; q < P; ++q) {
-        const bool skip = q == me && !c->self_coll;
-        sc[q] = skip ? 0 : (size_t)g.send[(size_t)q * C + k] * 2;
-        rc[q] = skip ? 0 : (size_t)g.recv[(size_t)q * C + k] * 2;
-        sd[q] = (size_t)(g.lo[k] + g.sdisp[(size_t)q * C + k]) * 2;
-        rdp[q] = (size_t)(r.recv_displs[q] + g.rpre[(size_t)q * C + k]) * 2;
-      }
-      {
-        Timer t(c, &r, LSB_K_WIRE, r.xstream);
-        LSB_TRY(coll_alltoallv_u64(c, r, reinterpret_cast<const uint64_t*>(Y[0]), sc.data(), sd.data(),
-                                   reinterpret_cast<uint64_t*>(r.R), rc.data(), rdp.data(), (size_t)seg * 2,
-                                   r.xstream));
-      }
+    // chunk k on the wire stream, once every local rank's pass has written it
+    for (size_t i = 0; i < nr; ++i) {
+      Rank& r = c->ranks[i];
+      HIP_TRY(hipSetDevice(r.dev));
+      for (Rank& s : c->ranks) HIP_TRY(hipStreamWaitEvent(r.xstream, s.ck_hi[k], 0));
+      chunk_wave(P, C, geo[i], r.recv_displs.data(), k, w[i]);
+    }
+    LSB_TRY(wire_step(c, w, Y, seg, &Rank::xstream));
+    for (Rank& r : c->ranks) {
+      HIP_TRY(hipSetDevice(r.dev));
       HIP_TRY(hipEventRecord(r.ck_wire[k], r.xstream));
     }
   }
@@ -791,22 +639,14 @@ int exchange_chunked(lsb_ctx* c, int digit, const std::vector<const uint32_t*>& 
   //    write X, also once every chunk pass has read X)
   for (size_t i = 0; i < nr; ++i) {
     Rank& r = c->ranks[i];
-    const ChunkGeom& g = geo[i];
-    const int me = r.rank;
     HIP_TRY(hipSetDevice(r.dev));
     r.A = Y[i];  // the records, ordered by the digit chunk by chunk (my own segment's source)
     r.B = X[i];  // the placement's destination
     if (!r.gather_next) HIP_TRY(hipStreamWaitEvent(r.pstream, r.ck_hi[C - 1], 0));
     for (int k = 0; k < C; ++k) {
       HIP_TRY(hipStreamWaitEvent(r.pstream, r.ck_wire[k], 0));
-      for (int s = 0; s < P; ++s) {
-        const int64_t cnt = g.recv[(size_t)s * C + k];
-        const int64_t k0 = r.recv_displs[s] + g.rpre[(size_t)s * C + k];
-        if (s == me && !self_in_r)
-          LSB_TRY(place_range(c, r, shift, s, Y[i] + g.lo[k] + g.sdisp[(size_t)me * C + k], k0, cnt));
-        else
-          LSB_TRY(place_range(c, r, shift, s, r.R + k0, k0, cnt));
-      }
+      chunk_wave(P, C, geo[i], r.recv_displs.data(), k, w[i]);
+      LSB_TRY(place_wave(c, r, shift, w[i], Y[i]));
     }
     HIP_TRY(hipEventRecord(r.xdone, r.xstream));
     HIP_TRY(hipStreamWaitEvent(r.stream, r.xdone, 0));
@@ -815,7 +655,7 @@ int exchange_chunked(lsb_ctx* c, int digit, const std::vector<const uint32_t*>& 
   }
   // Every rank's copies out of Y must be done before any rank's next pass
   // rewrites it (loopback; RCCL ranks wait for their own wire stream above).
-  if (loop)
+  if (c->mode == Mode::kLoopback)
     for (Rank& r : c->ranks) {
       HIP_TRY(hipSetDevice(r.dev));
       HIP_TRY(hipStreamSynchronize(r.stream));

@@ -11,6 +11,8 @@
 //   lsb_wholekey.cpp  the whole-key exchange (splitter search, one all-to-all,
 //                     merge of the P runs)
 //   lsb_abi.cpp       the extern "C" entry points and the host planners
+//   lsb_xgeom.h       host-only exchange geometry (checked plan, waves); no
+//                     device header, so host tools can include it alone
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -25,6 +27,7 @@
 
 #include "../../include/lsb.h"
 #include "lsb_kernels.h"
+#include "lsb_xgeom.h"
 
 namespace lsb_rt {
 
@@ -230,8 +233,7 @@ struct lsb_ctx {
 namespace lsb_rt {
 
 // ---- errors (lsb_context.cpp) ------------------------------------------------
-// Records `what: detail` for lsb_strerror and returns `code`.
-int fail(int code, const char* what, const char* detail);
+// fail(code, what, detail) is declared in lsb_xgeom.h.
 const std::string& last_error();
 
 inline int64_t div_ceil(int64_t x, int64_t y) { return (x + y - 1) / y; }
@@ -398,18 +400,6 @@ void os_profile_report();
 // (the whole-key exchange's owner slices).
 inline int64_t part(int64_t n, int j, int slices) { return n * j / slices; }
 
-// Part j of a per-digit exchange segment of n records cut into `slices`
-// halving parts: n/2, n/4, ..., and the last two n / 2^(slices-1) each.  A
-// slice is placed (or counted) while the next one is on the wire, so what
-// runs after the wire goes quiet is the last slice's placement: 1/16 of the
-// records at 5 slices where equal slices leave 1/4 at 4.
-// Sender and receiver cut a segment alike (send_counts[q] at s equals
-// recv_counts[s] at q).
-inline int64_t slice_part(int64_t n, int j, int slices) {
-  if (j >= slices) return n;
-  return j >= 63 ? n : n - (n >> j);
-}
-
 // Slices of an exchange: the option, else 5 halving slices per exchange digit,
 // or 8 equal slices for the whole-key exchange, whose one all-to-all carries
 // every record: its last slice's merge (ceil(log2 P) levels) is the tail
@@ -431,6 +421,12 @@ int exchange_digit(lsb_ctx* c, int digit);
 bool in_buffers(const Rank& q, const Elem* p, int64_t cnt);
 int copy_range(const lsb_ctx* c, Rank& dst_rank, Elem* dst, const Rank& src_rank, const Elem* src, int64_t cnt,
                hipStream_t s);
+// One all-to-all-v step of every exchange: every local rank's wave w[i] moves
+// out of its src[i] into its R on its stream `st` (Rank::stream or
+// Rank::xstream), timed as LSB_K_WIRE.  Loopback: one copy_range per pair;
+// one rank per process: one coll_alltoallv_u64, cut by `bound` records.
+int wire_step(lsb_ctx* c, const std::vector<Wave>& w, const std::vector<Elem*>& src, int64_t bound,
+              hipStream_t Rank::*st);
 // The per-digit exchange in chunks: digit `digit` (16 bits) whose low-byte
 // pass has run (A sorted by the low byte; lo_hist its input's sub-array
 // histogram on each rank), high-byte passes chunk by chunk, each chunk's
@@ -442,20 +438,8 @@ int sort_exchange_onesweep(lsb_ctx* c);
 
 // ---- whole-key exchange (lsb_wholekey.cpp) ------------------------------------
 
-// Cut positions of the exchange: owner q's block [q * per, q * per + here_q)
-// is cut into S slices (sub-blocks) at q * per + part(here_q, j, S); cut k =
-// q * S + j, plus k = P * S at n.  Every cut strictly inside (0, n) is a
-// target of the splitter search.  S = 1 gives the owner boundaries q * per.
-// Slices let the owner merge slice j while slice j + 1 is on the wire.
-struct MergeGeom {
-  int S = 1;
-  std::vector<int64_t> pos;   // [P * S + 1] global cut positions, nondecreasing
-  std::vector<int> target;    // cut indices k with 0 < pos[k] < n (splitter targets)
-};
-MergeGeom merge_geometry(int64_t n, int P, int slices);
-int merge_cuts(int64_t n, int P, const MergeGeom& g, const uint64_t* fin, std::vector<int64_t>& cut);
-int merge_owner_counts(int64_t n, int P, int me, const MergeGeom& g, const std::vector<int64_t>& cut,
-                       int64_t* sc, int64_t* sd, int64_t* rc, int64_t* rd);
+// The cut geometry (MergeGeom, merge_geometry, merge_cuts, merge_owner_counts)
+// is declared in lsb_xgeom.h.
 int merge_sort(lsb_ctx* c);
 
 }  // namespace lsb_rt

@@ -118,30 +118,6 @@ int merge_ensure(lsb_ctx* c, Rank& r, const MergeGeom& g) {
 }
 
 
-// Records of source s in owner r's slice j, where they sit in R, and the
-// slice's output range [lo, hi) of r's block.
-struct SliceRun {
-  int64_t len, roff;
-};
-
-void slice_runs(const lsb_ctx* c, const Rank& r, const MergeGeom& g, int j, std::vector<SliceRun>& out,
-                int64_t* lo, int64_t* hi) {
-  const size_t K1 = g.pos.size();
-  const int64_t base = (int64_t)r.rank * c->per;
-  const size_t k = (size_t)r.rank * g.S + j;
-  *lo = g.pos[k] - base;
-  *hi = g.pos[k + 1] - base;
-  if (*lo < 0) *lo = 0;
-  if (*hi < *lo) *hi = *lo;
-  out.resize(c->P);
-  int64_t off = *lo;
-  for (int s = 0; s < c->P; ++s) {
-    out[s].len = r.mcut[s * K1 + k + 1] - r.mcut[s * K1 + k];
-    out[s].roff = off;
-    off += out[s].len;
-  }
-}
-
 // Levels of the merge tree over `runs` runs (a single run is one copy level).
 int merge_levels(size_t runs) {
   int L = 0;
@@ -149,29 +125,25 @@ int merge_levels(size_t runs) {
   return L > 0 ? L : 1;
 }
 
-// Merge slice j of owner r on r.pstream: its P runs (source order; my own
-// straight out of A) -> F[lo, hi), F = B or R.  A tree of stable two-way
+// Merge a slice of owner r (its owner_wave w and output range [lo, hi)) on
+// r.pstream: its P runs (source order; my own straight out of A) ->
+// F[lo, hi), F = B or R.  A tree of stable two-way
 // merges, one launch per level, adjacent runs paired so the lower ranks stay
 // on the left; level l writes B (l even) or R (l odd): the slice's own region
 // of R is free once level 0 has read it, and A, still being sent from, is
 // never written.  A result that ends in the other buffer is copied to F
 // (only slices with fewer non-empty runs than the rest).
-int merge_slice(lsb_ctx* c, Rank& r, const MergeGeom& g, int j, Elem* F) {
+int merge_slice(lsb_ctx* c, Rank& r, const Wave& w, int64_t lo, int64_t hi, Elem* F) {
   struct Run {
     const Elem* p;
     int64_t n;
   };
-  std::vector<SliceRun> sr;
-  int64_t lo = 0, hi = 0;
-  slice_runs(c, r, g, j, sr, &lo, &hi);
   if (hi == lo) return LSB_OK;
-  const size_t K1 = g.pos.size();
   std::vector<Run> runs;
   for (int s = 0; s < c->P; ++s) {
-    if (sr[s].len == 0) continue;
+    if (w.rcnt[s] == 0) continue;
     const bool own = s == r.rank && !(c->self_coll && c->mode != Mode::kLoopback);
-    const Elem* p = own ? r.A + r.mcut[s * K1 + (size_t)r.rank * g.S + j] : r.R + sr[s].roff;
-    runs.push_back({p, sr[s].len});
+    runs.push_back({own ? r.A + w.soff[s] : r.R + w.roff[s], w.rcnt[s]});
   }
   Timer t(c, &r, LSB_K_PLACE, r.pstream);
   // 3 merge workgroups per CU (max_chunks = 2 per CU): 60 KiB of LDS, so
@@ -211,11 +183,11 @@ int merge_slice(lsb_ctx* c, Rank& r, const MergeGeom& g, int j, Elem* F) {
 
 // Slice j of the all-to-all has arrived on r.stream: merge it on r.pstream
 // while the next slice is on the wire.
-int merge_slice_async(lsb_ctx* c, Rank& r, const MergeGeom& g, int j, Elem* F) {
+int merge_slice_async(lsb_ctx* c, Rank& r, const Wave& w, int64_t lo, int64_t hi, Elem* F) {
   HIP_TRY(hipSetDevice(r.dev));
   HIP_TRY(hipEventRecord(r.pevent, r.stream));
   HIP_TRY(hipStreamWaitEvent(r.pstream, r.pevent, 0));
-  return merge_slice(c, r, g, j, F);
+  return merge_slice(c, r, w, lo, hi, F);
 }
 
 int exchange_merge(lsb_ctx* c) {
@@ -267,8 +239,11 @@ int exchange_merge(lsb_ctx* c) {
   //    in A), then the slice's merge on the placement stream.  The merged
   //    block lands in B or R, whichever the last level of a P-run tree writes.
   const bool final_b = (merge_levels((size_t)P) - 1) % 2 == 0;
-  std::vector<SliceRun> sr;
-  int64_t lo = 0, hi = 0;
+  const size_t nr = c->ranks.size();
+  std::vector<Wave> w(nr);
+  std::vector<int64_t> lo(nr), hi(nr);
+  std::vector<Elem*> src(nr);
+  for (size_t i = 0; i < nr; ++i) src[i] = c->ranks[i].A;
   // The longest range any source sends to any (owner, slice): every rank holds
   // every source's cuts, so all cut their RCCL calls alike (coll_alltoallv_u64).
   int64_t run_max = 0;
@@ -278,38 +253,12 @@ int exchange_merge(lsb_ctx* c) {
       for (size_t k = 0; k + 1 < K1; ++k) run_max = std::max(run_max, mc[s * K1 + k + 1] - mc[s * K1 + k]);
   }
   for (int j = 0; j < g.S; ++j) {
-    if (c->mode == Mode::kLoopback) {
-      for (Rank& q : c->ranks) {
-        HIP_TRY(hipSetDevice(q.dev));
-        Timer t(c, &q, LSB_K_WIRE);
-        slice_runs(c, q, g, j, sr, &lo, &hi);
-        for (Rank& s : c->ranks) {
-          if (s.rank == q.rank || sr[s.rank].len == 0) continue;
-          LSB_TRY(copy_range(c, q, q.R + sr[s.rank].roff, s, s.A + q.mcut[s.rank * K1 + (size_t)q.rank * g.S + j],
-                             sr[s.rank].len, q.stream));
-        }
-      }
-      for (Rank& q : c->ranks) LSB_TRY(merge_slice_async(c, q, g, j, final_b ? q.B : q.R));
-    } else {
-      Rank& r = c->ranks[0];
-      HIP_TRY(hipSetDevice(r.dev));
-      slice_runs(c, r, g, j, sr, &lo, &hi);
-      std::vector<size_t> sc(P), sd(P), rc(P), rdp(P);
-      for (int q = 0; q < P; ++q) {
-        const size_t kq = (size_t)q * g.S + j;
-        const bool skip = q == r.rank && !c->self_coll;  // own range stays in A
-        sc[q] = skip ? 0 : (size_t)(r.mcut[(size_t)r.rank * K1 + kq + 1] - r.mcut[(size_t)r.rank * K1 + kq]) * 2;
-        sd[q] = (size_t)r.mcut[(size_t)r.rank * K1 + kq] * 2;
-        rc[q] = skip ? 0 : (size_t)sr[q].len * 2;
-        rdp[q] = (size_t)sr[q].roff * 2;
-      }
-      {
-        Timer t(c, &r, LSB_K_WIRE);
-        LSB_TRY(coll_alltoallv_u64(c, r, reinterpret_cast<const uint64_t*>(r.A), sc.data(), sd.data(),
-                                   reinterpret_cast<uint64_t*>(r.R), rc.data(), rdp.data(),
-                                   (size_t)run_max * 2));
-      }
-      LSB_TRY(merge_slice_async(c, r, g, j, final_b ? r.B : r.R));
+    for (size_t i = 0; i < nr; ++i)
+      owner_wave(P, c->ranks[i].rank, c->per, g, c->ranks[i].mcut, j, w[i], &lo[i], &hi[i]);
+    LSB_TRY(wire_step(c, w, src, run_max, &Rank::stream));
+    for (size_t i = 0; i < nr; ++i) {
+      Rank& r = c->ranks[i];
+      LSB_TRY(merge_slice_async(c, r, w[i], lo[i], hi[i], final_b ? r.B : r.R));
     }
   }
   // 4. the merged block (B or R) becomes A: every rank's sends out of A are done

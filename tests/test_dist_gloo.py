@@ -1,7 +1,7 @@
 """The N > 1 path with real processes on CPU (world size 2, gloo).
 
 Each rank runs the runtime's per-pass protocol (lsb_exchange.cpp
-exchange_rccl) with gloo standing in for RCCL and the oracle's local pass
+exchange_sliced) with gloo standing in for RCCL and the oracle's local pass
 standing in for the device kernels:
   local stable pass -> all-gather of bucket counts -> lsb_plan_exchange
   (the product's host planner) -> point-to-point send/recv of 16-byte

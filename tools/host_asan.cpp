@@ -4,15 +4,21 @@
 //   - lsb_plan_exchange on random, skewed, empty and n < P count matrices:
 //     conservation (sum send = sum recv = here), displacement prefix sums,
 //     every live placement offset inside [0, here);
+//   - the exchanges' host geometry (csrc/lsb_xgeom.h) on the same matrices:
+//     the checked plan accepts every host plan and refuses corrupted ones;
+//     the slice, chunk and whole-key waves tile every send and receive range
+//     once, and sender and receiver agree at every step;
 //   - every argument check that returns before a device call;
 //   - lsb_create / lsb_create_rank_ops with no usable device: the failure
 //     path tears down a half-built context (no leak, no double free).
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <random>
 #include <vector>
 
 #include "lsb.h"
+#include "lsb_xgeom.h"
 
 static int fails = 0;
 #define CHECK(c, what)                                    \
@@ -22,6 +28,11 @@ static int fails = 0;
       ++fails;                                            \
     }                                                     \
   } while (0)
+
+typedef std::vector<std::vector<int64_t>> PerRank;  // [rank][peer]
+static void checked_plan_case(int P, int64_t here, const std::vector<int64_t>& sc, const std::vector<int64_t>& sd,
+                              const std::vector<int64_t>& rc, const std::vector<int64_t>& rd);
+static void slice_wave_case(int P, const PerRank& sc, const PerRank& sd, const PerRank& rc, const PerRank& rd);
 
 static void plan_case(std::mt19937_64& rng, int64_t n, int P, int nb, bool skew) {
   std::vector<int64_t> hist((size_t)P * nb, 0);
@@ -48,7 +59,9 @@ static void plan_case(std::mt19937_64& rng, int64_t n, int P, int nb, bool skew)
     }
     CHECK(ss == lsb_here(n, P, me), "send total = here");
     CHECK(rs == lsb_here(n, P, me), "recv total = here");
+    checked_plan_case(P, lsb_here(n, P, me), sc[me], sd[me], rc[me], rd[me]);
   }
+  slice_wave_case(P, sc, sd, rc, rd);
   // Receiver me: record k of the segment from s is record sd[s][me] + (k - rd[me][s])
   // of s's bucket-ordered buffer; its slot place[me][s][bucket] + k must
   // cover [0, here) exactly once.
@@ -75,6 +88,201 @@ static void plan_case(std::mt19937_64& rng, int64_t n, int P, int nb, bool skew)
   }
 }
 
+// The exchange's checked plan (lsb_xgeom.h) on rank me's host plan: accepted,
+// same displacements; five corruptions of it are refused.
+static void checked_plan_case(int P, int64_t here, const std::vector<int64_t>& sc, const std::vector<int64_t>& sd,
+                              const std::vector<int64_t>& rc, const std::vector<int64_t>& rd) {
+  std::vector<int64_t> good(sc);
+  good.insert(good.end(), rc.begin(), rc.end());
+  std::vector<int64_t> o[4];
+  for (auto& v : o) v.assign(P, -7);
+  auto run = [&](const std::vector<int64_t>& counts) {
+    return lsb_rt::checked_plan(counts.data(), P, here, o[0].data(), o[1].data(), o[2].data(), o[3].data());
+  };
+  CHECK(run(good) == LSB_OK, "checked plan accepts the host plan");
+  CHECK(o[0] == sc && o[1] == sd && o[2] == rc && o[3] == rd, "checked plan = host plan");
+  std::vector<int64_t> bad(good);
+  bad[0] = -1;
+  CHECK(run(bad) == LSB_ERR_STATE, "negative count");
+  bad = good;
+  bad[0] += 1;
+  CHECK(run(bad) == LSB_ERR_STATE, "send total = here + 1");
+  bad = good;
+  bad[2 * P - 1] = INT64_MAX;
+  CHECK(run(bad) == LSB_ERR_STATE, "count = INT64_MAX");
+  bad[0] = INT64_MAX;
+  CHECK(run(bad) == LSB_ERR_STATE, "two counts = INT64_MAX");
+  if (here > 0) {
+    bad = good;
+    for (int q = 0; q < P; ++q)
+      if (bad[P + q] > 0) {
+        bad[P + q] -= 1;
+        break;
+      }
+    CHECK(run(bad) == LSB_ERR_STATE, "recv total = here - 1");
+    bad.assign(2 * P, 0);
+    CHECK(run(bad) == LSB_ERR_STATE, "all counts zero");
+  }
+}
+
+// waves[r][j]: rank r's wave of step j.  Over the steps, in order, the waves
+// tile every pair's send range [sd, +sc) and receive range [rd, +rc) exactly
+// once, and at every step the sender's count is the receiver's.
+typedef std::vector<std::vector<lsb_rt::Wave>> Waves;
+static void waves_tile(int P, const Waves& waves, const PerRank& sc, const PerRank& sd, const PerRank& rc,
+                       const PerRank& rd) {
+  for (int s = 0; s < P; ++s)
+    for (int q = 0; q < P; ++q) {
+      int64_t scur = sd[s][q], rcur = rd[q][s];
+      for (size_t j = 0; j < waves[s].size(); ++j) {
+        const lsb_rt::Wave &ws = waves[s][j], &wq = waves[q][j];
+        CHECK(ws.scnt[q] >= 0 && ws.soff[q] == scur, "send parts in order");
+        CHECK(wq.rcnt[s] >= 0 && wq.roff[s] == rcur, "recv parts in order");
+        CHECK(ws.scnt[q] == wq.rcnt[s], "sender and receiver agree");
+        scur += ws.scnt[q];
+        rcur += wq.rcnt[s];
+      }
+      CHECK(scur == sd[s][q] + sc[s][q], "send range covered");
+      CHECK(rcur == rd[q][s] + rc[q][s], "recv range covered");
+    }
+}
+
+static void slice_wave_case(int P, const PerRank& sc, const PerRank& sd, const PerRank& rc, const PerRank& rd) {
+  for (int slices : {1, 2, 5, 8, 65}) {  // 65: slice_part's j >= 63 guard
+    Waves waves(P, std::vector<lsb_rt::Wave>(slices));
+    for (int r = 0; r < P; ++r)
+      for (int j = 0; j < slices; ++j)
+        lsb_rt::slice_wave(P, sc[r].data(), sd[r].data(), rc[r].data(), rd[r].data(), j, slices, waves[r][j]);
+    waves_tile(P, waves, sc, sd, rc, rd);
+  }
+}
+
+// exchange_chunked's geometry: random records of source s for owner q in
+// chunk k (empty chunks and empty peers among them; every rank sends as many
+// as it receives), the low byte's histogram and the plan totals they imply.
+static void chunk_case(std::mt19937_64& rng, int P, int C) {
+  const int buckets = 256, subs = 8, lw = buckets / C;
+  std::vector<int64_t> m((size_t)P * P * C, 0);  // [s][q][k]
+  for (int s = 0; s < P; ++s)
+    for (int q = s; q < P; ++q)
+      for (int k = 0; k < C; ++k) {
+        const bool empty = rng() % 4 == 0 || (s + q) % 3 == 2 || (P > 1 && k == 1);
+        const int64_t v = empty ? 0 : (int64_t)(rng() % 50);
+        m[((size_t)s * P + q) * C + k] += v;
+        if (q != s) m[((size_t)q * P + s) * C + k] += v;
+      }
+  std::vector<lsb_rt::ChunkGeom> geo(P);
+  PerRank ck(P), sc(P), sd(P), rc(P), rd(P);
+  std::vector<int64_t> here(P, 0);
+  std::vector<std::vector<uint32_t>> lo_hist(P);
+  for (int me = 0; me < P; ++me) {
+    ck[me].assign((size_t)2 * P * C, 0);
+    sc[me].assign(P, 0), sd[me].assign(P, 0), rc[me].assign(P, 0), rd[me].assign(P, 0);
+    lo_hist[me].assign((size_t)subs * buckets, 0);
+    for (int q = 0; q < P; ++q)
+      for (int k = 0; k < C; ++k) {
+        const int64_t snd = m[((size_t)me * P + q) * C + k], rcv = m[((size_t)q * P + me) * C + k];
+        ck[me][(size_t)q * C + k] = snd;
+        ck[me][(size_t)P * C + (size_t)q * C + k] = rcv;
+        sc[me][q] += snd;
+        rc[me][q] += rcv;
+        here[me] += snd;
+        for (int64_t i = 0; i < snd; ++i) ++lo_hist[me][(rng() % subs) * buckets + k * lw + rng() % lw];
+      }
+    for (int q = 1; q < P; ++q) rd[me][q] = rd[me][q - 1] + rc[me][q - 1];
+    CHECK(lsb_rt::chunk_geom(P, C, here[me], lo_hist[me].data(), buckets, subs, ck[me].data(), sc[me].data(),
+                             rc[me].data(), geo[me]) == LSB_OK, "chunk_geom accepts");
+  }
+  Waves waves(P, std::vector<lsb_rt::Wave>(C));
+  for (int r = 0; r < P; ++r) {
+    int64_t cur = 0;  // a rank's sends, chunk by chunk and owner by owner, tile its block
+    for (int k = 0; k < C; ++k) {
+      lsb_rt::chunk_wave(P, C, geo[r], rd[r].data(), k, waves[r][k]);
+      for (int q = 0; q < P; ++q) {
+        CHECK(waves[r][k].soff[q] == cur, "chunk sends tile the block");
+        cur += waves[r][k].scnt[q];
+      }
+    }
+    CHECK(cur == here[r], "chunk sends cover the block");
+  }
+  for (int r = 0; r < P; ++r)
+    for (int q = 0; q < P; ++q) {
+      int64_t sent = 0, rcur = rd[r][q];
+      for (int k = 0; k < C; ++k) {
+        CHECK(waves[r][k].roff[q] == rcur, "chunk receives tile the source's range");
+        CHECK(waves[q][k].scnt[r] == waves[r][k].rcnt[q], "sender and receiver agree");
+        rcur += waves[r][k].rcnt[q];
+        sent += waves[r][k].scnt[q];
+      }
+      CHECK(rcur == rd[r][q] + rc[r][q] && sent == sc[r][q], "chunk counts add up to the plan");
+    }
+  // one count off by one, or negative: refused
+  lsb_rt::ChunkGeom g;
+  for (int64_t delta : {int64_t(1), int64_t(-1), INT64_MIN}) {
+    std::vector<int64_t> bad(ck[0]);
+    int64_t& x = bad[rng() % bad.size()];
+    x = delta == INT64_MIN ? -5 : x + delta;
+    CHECK(lsb_rt::chunk_geom(P, C, here[0], lo_hist[0].data(), buckets, subs, bad.data(), sc[0].data(),
+                             rc[0].data(), g) == LSB_ERR_STATE, "chunk_geom refuses a wrong count");
+  }
+}
+
+// The whole-key exchange's owner slices: P sorted blocks with ties, the cuts
+// from the counts a finished splitter search gives.
+static void wholekey_case(std::mt19937_64& rng, int64_t n, int P, int slices) {
+  using namespace lsb_rt;
+  std::vector<std::vector<uint64_t>> blk(P);
+  std::vector<uint64_t> all;
+  for (int s = 0; s < P; ++s) {
+    for (int64_t i = 0; i < lsb_here(n, P, s); ++i) blk[s].push_back(rng() % 40);
+    std::sort(blk[s].begin(), blk[s].end());
+    all.insert(all.end(), blk[s].begin(), blk[s].end());
+  }
+  std::sort(all.begin(), all.end());
+  const MergeGeom g = merge_geometry(n, P, slices);
+  const int Q = (int)g.target.size();
+  std::vector<uint64_t> fin((size_t)P * Q * 2 + 1, 0);
+  for (int t = 0; t < Q; ++t) {
+    const uint64_t key = all[(size_t)g.pos[g.target[t]]];
+    for (int s = 0; s < P; ++s) {
+      fin[((size_t)s * Q + t) * 2] = std::lower_bound(blk[s].begin(), blk[s].end(), key) - blk[s].begin();
+      fin[((size_t)s * Q + t) * 2 + 1] = std::upper_bound(blk[s].begin(), blk[s].end(), key) - blk[s].begin();
+    }
+  }
+  std::vector<int64_t> cut;
+  CHECK(merge_cuts(n, P, g, fin.data(), cut) == LSB_OK, "merge_cuts ok");
+  PerRank sc(P), sd(P), rc(P), rd(P);
+  Waves waves(P, std::vector<Wave>(g.S));
+  for (int me = 0; me < P; ++me) {
+    sc[me].resize(P), sd[me].resize(P), rc[me].resize(P), rd[me].resize(P);
+    CHECK(merge_owner_counts(n, P, me, g, cut, sc[me].data(), sd[me].data(), rc[me].data(), rd[me].data()) == LSB_OK,
+          "merge_owner_counts ok");
+    int64_t end = 0;
+    for (int j = 0; j < g.S; ++j) {
+      int64_t lo = -1, hi = -1;
+      owner_wave(P, me, lsb_per_rank(n, P), g, cut, j, waves[me][j], &lo, &hi);
+      CHECK(lo == end && hi >= lo && waves[me][j].roff[0] == lo, "slices follow each other");
+      for (int s = 0; s < P; ++s) lo += waves[me][j].rcnt[s];
+      CHECK(lo == hi, "a slice's runs fill its output range");
+      end = hi;
+    }
+    CHECK(end == lsb_here(n, P, me), "slices cover the block");
+  }
+  // The totals over j are merge_owner_counts'; source s's slice j follows its
+  // slice j - 1 in A, but lies after every source's slice j - 1 in R.
+  for (int s = 0; s < P; ++s)
+    for (int q = 0; q < P; ++q) {
+      int64_t scur = sd[s][q], got = 0;
+      for (int j = 0; j < g.S; ++j) {
+        CHECK(waves[s][j].soff[q] == scur, "send parts in order");
+        CHECK(waves[s][j].scnt[q] == waves[q][j].rcnt[s], "sender and receiver agree");
+        scur += waves[s][j].scnt[q];
+        got += waves[q][j].rcnt[s];
+      }
+      CHECK(scur == sd[s][q] + sc[s][q] && got == rc[q][s], "owner slices add up to the owner counts");
+    }
+}
+
 static int noop_ag(void*, const void*, void*, size_t) { return 0; }
 static int noop_a2a(void*, const void*, const size_t*, const size_t*, void*, const size_t*,
                     const size_t*) { return 0; }
@@ -90,6 +298,11 @@ int main() {
       for (int nb : {256, 65536})
         for (bool skew : {false, true})
           if (!(nb == 65536 && P == 64)) plan_case(rng, n, P, nb, skew);
+  for (int C : {2, 4, 8})
+    for (int P : {1, 3, 8}) chunk_case(rng, P, C);
+  for (int64_t n : {int64_t(5), int64_t(1000), int64_t(1003)})
+    for (int P : {2, 3, 8})
+      for (int S : {1, 4}) wholekey_case(rng, n, P, S);
 
   // argument checks
   std::vector<int64_t> h(2 * 256, 0), o(2), pl(2 * 256);
