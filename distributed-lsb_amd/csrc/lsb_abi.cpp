@@ -237,6 +237,10 @@ int lsb_set_option(lsb_ctx_t* c, int option, int64_t value) {
     case LSB_OPT_REGION_FIRST:
       c->region = value != 0;
       return LSB_OK;
+    case LSB_OPT_PACK_VALUES:
+      if (value < 0 || value > 2) return fail(LSB_ERR_INVALID, "lsb_set_option", "pack values must be 0, 1 or 2");
+      c->pack_values = (int)value;
+      return LSB_OK;
     case LSB_OPT_EXCHANGE_PEER:
       c->peer = value != 0;
       return LSB_OK;
@@ -303,6 +307,7 @@ int lsb_generate_ex(lsb_ctx_t* c, int dist, double param) {
     HIP_TRY(lsb::launch_pcg_fill(r.A, c->per, (uint64_t)r.rank, (uint64_t)r.rank * c->per, g,
                                  r.stream));
   }
+  c->broken = false;  // A holds whole records again
   return lsb_sync(c);
 }
 
@@ -369,6 +374,7 @@ int sort_body(lsb_ctx* c) {
   c->last_local_passes = c->last_exchanges = 0;
   c->last_varying = ~0ull;
   c->last_first = LSB_FIRST_COUNT;
+  c->last_records = LSB_RECORDS_FULL;
   c->pass_cursor = 0;
   c->cur_pass = 0;
   if (c->bits == 64 && exchanging(c)) {
@@ -404,6 +410,8 @@ int sort_body(lsb_ctx* c) {
 
 int lsb_sort(lsb_ctx_t* c) {
   LSB_TRY(check_ctx(c));
+  if (c->broken)
+    return fail(LSB_ERR_STATE, "lsb_sort", "an earlier sort failed and left packed records in A; load the input again");
   const int rc = sort_body(c);
   if (rc != LSB_OK) quiesce(c);
   return rc;
@@ -421,6 +429,13 @@ int lsb_get_first_pass(lsb_ctx_t* c, int* form) {
   LSB_TRY(check_ctx(c));
   if (!form) return fail(LSB_ERR_INVALID, "lsb_get_first_pass", "null");
   *form = c->last_first;
+  return LSB_OK;
+}
+
+int lsb_get_last_records(lsb_ctx_t* c, int* form) {
+  LSB_TRY(check_ctx(c));
+  if (!form) return fail(LSB_ERR_INVALID, "lsb_get_last_records", "null");
+  *form = c->last_records;
   return LSB_OK;
 }
 

@@ -369,6 +369,11 @@ lsb_ctx* new_ctx(int64_t n_total, int num_ranks, int radix_bits) {
   // LSB_REGION_FIRST=0: contexts start with the option off (A/B runs of
   // programs that do not set options, e.g. bench.py).
   if (const char* e = getenv("LSB_REGION_FIRST")) c->region = atoi(e) != 0;
+  // LSB_PACK_VALUES=0|1|2: the same for LSB_OPT_PACK_VALUES.
+  if (const char* e = getenv("LSB_PACK_VALUES")) {
+    const int v = atoi(e);
+    if (v >= 0 && v <= 2) c->pack_values = v;
+  }
   // LSB_EXCHANGE_CHUNKS=C: contexts start with LSB_OPT_EXCHANGE_CHUNKS = C
   // (A/B runs of programs that do not set options); LSB_XCHUNK_RESERVE: the
   // chunk passes' grid leaves that many workgroups to the wire (experiments).

@@ -13,6 +13,13 @@ struct alignas(16) Elem {
   uint64_t val;
 };
 static_assert(sizeof(Elem) == 16, "16-byte records");
+// A record between two passes of a sort whose values all fit 32 bits
+// (LSB_OPT_PACK_VALUES): 12 bytes, in the same record buffers.
+struct alignas(4) Packed {
+  uint32_t klo, khi;  // the key's low and high words
+  uint32_t val;
+};
+static_assert(sizeof(Packed) == 12, "12-byte packed records");
 
 constexpr int kDigitBits = 8;                 // one local pass = one 8-bit digit
 constexpr int kBuckets = 1 << kDigitBits;     // 256
@@ -252,12 +259,14 @@ struct RegionPass {
   int64_t cap = 0;                    // slots per region
   uint32_t* counts = nullptr;         // [kRegions] records per region
   uint32_t* ovf = nullptr;            // mode 1: set when a region overflows
+  uint32_t* wide = nullptr;           // mode 1 writing packed records: set when a value needs over 32 bits
 };
 // Sample of the sort's first digit (the regional first pass's go / no-go):
 // 256 workgroups read one tile each, spread over the m records; hist[256]
 // (zeroed here) gets the tiles' digit counts at `shift`, span[2] (zeroed
-// here) the OR of their keys and complements.
-hipError_t launch_sample(const Elem* A, int64_t m, int shift, uint32_t* hist, uint64_t* span,
+// here) the OR of their keys and complements, *wide (zeroed here) the OR of
+// their values' high words.
+hipError_t launch_sample(const Elem* A, int64_t m, int shift, uint32_t* hist, uint64_t* span, uint32_t* wide,
                          hipStream_t s);
 struct OnesweepExtra {
   uint64_t* totals = nullptr;
@@ -268,6 +277,12 @@ struct OnesweepExtra {
   bool probe = false;  // the placement probe's pass (a last pass, launched as k_onesweep_probe)
   const RegionPass* region = nullptr;  // with region_mode 1 or 2: the regional layout
   int region_mode = 0;  // 1: write it (needs a next digit); 2: read it (sub_hist over its tiles)
+  // Packed records (regional LSD sorts only: whole stage, nothing else set).
+  // `in` / `out` then point at Packed records.  The four forms: region_mode 1
+  // Elem -> Packed (values truncated; region->wide says when that lost bits),
+  // region_mode 2 and a next-counting pass Packed -> Packed, and a last pass
+  // Packed -> Elem.
+  bool pack_in = false, pack_out = false;
 };
 // The runtime's choice of OnesweepExtra::halves for a rank, from a digit's
 // sub-array histogram (kOnesweepSubs x 256 counts of m records): 2 when one
@@ -386,6 +401,8 @@ hipError_t launch_merge_level(const MergeLevel& level, int64_t* path, int grid, 
 // first_bad must hold UINT64_MAX before the launch; receives min bad global index.
 // cnt records src -> dst on one device (loopback exchange copies).
 hipError_t launch_copy_records(Elem* dst, const Elem* src, int64_t cnt, hipStream_t s);
+// cnt packed records src -> Elem records dst (distinct buffers).
+hipError_t launch_unpack(Elem* dst, const Packed* src, int64_t cnt, hipStream_t s);
 hipError_t launch_verify(const Elem* A, int64_t here, int64_t gbase, int64_t n, int64_t per,
                          KeyGen gen, unsigned long long* first_bad, hipStream_t s);
 

@@ -134,6 +134,32 @@ __device__ __forceinline__ void store_elem(Elem* p, const Elem& e) {
   *reinterpret_cast<ulonglong2*>(p) = make_ulonglong2(e.key, e.val);
 }
 
+// Packed records (lsb_kernels.h): 4-byte aligned, so the three words are one
+// 12-byte access (global_load_dwordx3 nt / global_store_dwordx3).
+__device__ __forceinline__ Packed load_elem_nt(const Packed* p) {
+  const uint32_t* w = reinterpret_cast<const uint32_t*>(p);
+  return Packed{__builtin_nontemporal_load(w), __builtin_nontemporal_load(w + 1), __builtin_nontemporal_load(w + 2)};
+}
+
+__device__ __forceinline__ void store_elem(Packed* p, const Packed& e) { *p = e; }
+
+// A record's key and value whatever its form, and a record of form R made
+// from them (a Packed record keeps the value's low word).
+__device__ __forceinline__ uint64_t rec_key(const Elem& e) { return e.key; }
+__device__ __forceinline__ uint64_t rec_key(const Packed& e) { return ((uint64_t)e.khi << 32) | e.klo; }
+__device__ __forceinline__ uint64_t rec_val(const Elem& e) { return e.val; }
+__device__ __forceinline__ uint64_t rec_val(const Packed& e) { return e.val; }
+template <typename R>
+__device__ __forceinline__ R make_rec(uint64_t key, uint64_t val);
+template <>
+__device__ __forceinline__ Elem make_rec<Elem>(uint64_t key, uint64_t val) {
+  return Elem{key, val};
+}
+template <>
+__device__ __forceinline__ Packed make_rec<Packed>(uint64_t key, uint64_t val) {
+  return Packed{(uint32_t)key, (uint32_t)(key >> 32), (uint32_t)val};
+}
+
 // Inclusive wave scan (64 lanes).
 template <typename T>
 __device__ __forceinline__ T wave_inclusive_scan(T v) {
@@ -856,7 +882,8 @@ constexpr int kSampleBlock = 256;
 constexpr int kSampleTiles = 256;
 __global__ __launch_bounds__(kSampleBlock) void k_sample(const Elem* __restrict__ A, int64_t m, int shift,
                                                          uint32_t* __restrict__ hist,
-                                                         unsigned long long* __restrict__ span) {
+                                                         unsigned long long* __restrict__ span,
+                                                         uint32_t* __restrict__ wide) {
   constexpr int IPT = kTile / kSampleBlock;
   __shared__ uint32_t h[kBuckets];
   h[threadIdx.x] = 0;
@@ -865,11 +892,13 @@ __global__ __launch_bounds__(kSampleBlock) void k_sample(const Elem* __restrict_
   const int64_t tb = (int64_t)blockIdx.x * TT / gridDim.x * kTile;
   const uint64_t* __restrict__ keys = reinterpret_cast<const uint64_t*>(A);
   uint64_t kor = 0, knor = 0;
+  uint32_t vhi = 0;  // OR of the values' high words (LSB_OPT_PACK_VALUES)
 #pragma unroll
   for (int i = 0; i < IPT; ++i) {
     const int64_t idx = tb + (int64_t)i * kSampleBlock + threadIdx.x;
     if (idx < m) {
       const uint64_t k = __builtin_nontemporal_load(keys + 2 * idx);
+      vhi |= (uint32_t)(__builtin_nontemporal_load(keys + 2 * idx + 1) >> 32);
       kor |= k;
       knor |= ~k;
       atomicAdd(&h[(uint32_t)(k >> shift) & (kBuckets - 1)], 1u);
@@ -884,6 +913,7 @@ __global__ __launch_bounds__(kSampleBlock) void k_sample(const Elem* __restrict_
     atomicOr(&span[0], (unsigned long long)kor);
     atomicOr(&span[1], (unsigned long long)knor);
   }
+  if (__ballot(vhi != 0) != 0 && lane_id() == 0) atomicOr(wide, 1u);
   __syncthreads();
   if (h[threadIdx.x]) atomicAdd(&hist[threadIdx.x], h[threadIdx.x]);
 }
@@ -977,9 +1007,14 @@ constexpr int kSegWin = LSB_SEG_WIN;
 // sub-array x starts at region (b, x)'s first slot plus the look-back sum,
 // and the next digit is counted over the regional layout's tiles.  RG = 2
 // reads that layout: tile t takes the valid prefix of its region's slots.
-template <int BLOCK, int IPT, bool NEXT, bool C16, int HALVES, bool SEG, bool GATHER, int RG>
+//
+// PIN / POUT (LSB_OPT_PACK_VALUES): the input / the output holds
+// Packed records (12 bytes: the key and the value's low word).  A packed
+// output is staged as keys and values apart (48 KiB instead of 64).  The
+// packing first pass (RG = 1, POUT) also reports a value that does not fit.
+template <int BLOCK, int IPT, bool NEXT, bool C16, int HALVES, bool SEG, bool GATHER, int RG, bool PIN, bool POUT>
 __device__ __forceinline__ void onesweep_body(
-    const Elem* __restrict__ in, Elem* __restrict__ out, int64_t m, int shift, int next_shift,
+    const Elem* __restrict__ in_, Elem* __restrict__ out_, int64_t m, int shift, int next_shift,
     const uint32_t* __restrict__ sub_hist, uint32_t* __restrict__ next_hist,
     uint32_t* __restrict__ status, uint32_t* __restrict__ tile_ctr, uint32_t epoch,
     uint32_t* __restrict__ err, uint64_t* __restrict__ totals,
@@ -989,6 +1024,12 @@ __device__ __forceinline__ void onesweep_body(
   static_assert(!SEG || (!NEXT && !C16 && HALVES == 1), "the segment pass: last pass, whole stage");
   static_assert(RG == 0 || (!C16 && HALVES == 1 && !SEG && !GATHER), "regional passes: plain whole stage");
   static_assert(RG != 1 || NEXT, "the regional first pass counts the next digit");
+  static_assert(!(PIN || POUT) || (!C16 && HALVES == 1 && !SEG && !GATHER), "packed records: plain whole stage");
+  static_assert(!(RG == 1 && PIN) && !(RG == 2 && !PIN && POUT), "only the first pass packs");
+  using RIn = typename std::conditional<PIN, Packed, Elem>::type;
+  using ROut = typename std::conditional<POUT, Packed, Elem>::type;
+  const RIn* __restrict__ in = reinterpret_cast<const RIn*>(in_);
+  ROut* __restrict__ out = reinterpret_cast<ROut*>(out_);
   // Thread t < 256 owns bucket t (counts, scan, look-back, offsets); with
   // BLOCK = 512 the other threads only load, rank, stage and write.
   static_assert(BLOCK % kBuckets == 0, "bucket threads");
@@ -997,7 +1038,9 @@ __device__ __forceinline__ void onesweep_body(
   using WC = typename std::conditional<(W > 4), uint16_t, uint32_t>::type;
 
   constexpr int HT = T / HALVES;                // staged records per half
-  __shared__ Elem stage[HT];                    // the ranked tile (64 KiB, or one half)
+  __shared__ Elem stage[POUT ? 1 : HT];         // the ranked tile (64 KiB, or one half)
+  __shared__ uint64_t skey[POUT ? HT : 1];      // POUT: its keys and values (48 KiB)
+  __shared__ uint32_t sval[POUT ? HT : 1];
   __shared__ WC wcnt[W][kBuckets];              // per-wave digit counters -> positions
   __shared__ int64_t delta[kBuckets];           // global dest = delta[digit] + tile position
   __shared__ uint32_t cut[NEXT ? kBuckets : 1];  // next-pass sub-array of a run: see below
@@ -1018,6 +1061,7 @@ __device__ __forceinline__ void onesweep_body(
   const int64_t TTn = RG == 1 ? rg.cap / T * kRegions : (m + T - 1) / T;
   const int64_t mcap = RG == 1 ? region_stride(rg.cap) * kRegions : m;
   uint32_t racc = 0;                     // RG = 1: thread t's count of region (t, cur_sub)
+  uint32_t vhi = 0;                      // packing pass: OR of the values' high words
   // Granule tags (bits 30-31): this launch's parity, and the prefix bit.
   constexpr uint32_t kValMask = kStatusValMask, kPreBit = 1u << 30;
   const uint32_t tag_agg = (epoch & 1u) << 31, tag_pre = tag_agg | kPreBit;
@@ -1159,7 +1203,7 @@ __device__ __forceinline__ void onesweep_body(
       tb = region_base(rg_reg, rg.cap) + (int64_t)rg_k * T;
     }
 
-    Elem e[IPT];
+    RIn e[IPT];
     const int wbase = w * 64 * IPT + (int)lane;
     if (GATHER) {
       const int dn = __builtin_amdgcn_readfirstlane(s_desc.n);
@@ -1202,7 +1246,7 @@ __device__ __forceinline__ void onesweep_body(
             for (int k = 1; k < kDescPieces; ++k) src = li >= st[k] ? pb[k] : src;
           }
           LSB_DASSERT(li >= nvalid || gather_in(gs, src + li));
-          e[i] = li < nvalid ? load_elem_nt(src + li) : Elem{0ull, 0ull};
+          if constexpr (GATHER) e[i] = li < nvalid ? load_elem_nt(src + li) : Elem{0ull, 0ull};
         }
       } else {
         // One record's search at a time (the scheduling barrier keeps the
@@ -1212,7 +1256,8 @@ __device__ __forceinline__ void onesweep_body(
         for (int i = 0; i < IPT; ++i) {
           const int li = wbase + i * 64;
           LSB_DASSERT(li >= nvalid || gather_in(gs, gather_search(gs, e0, e1, tb + li)));
-          e[i] = li < nvalid ? load_elem_nt(gather_search(gs, e0, e1, tb + li)) : Elem{0ull, 0ull};
+          if constexpr (GATHER)
+            e[i] = li < nvalid ? load_elem_nt(gather_search(gs, e0, e1, tb + li)) : Elem{0ull, 0ull};
           __builtin_amdgcn_sched_barrier(0);
         }
       }
@@ -1229,7 +1274,17 @@ __device__ __forceinline__ void onesweep_body(
 #pragma unroll
       for (int i = 0; i < IPT; ++i) {
         const int li = wbase + i * 64;
-        e[i] = RG == 2 || li < nvalid ? load_elem_nt(in + tb + li) : Elem{0ull, 0ull};
+        if (PIN && RG != 2) {
+          // Packed input: every lane loads (a lane past the tile's end reads
+          // its last record again) and the record is zeroed afterwards.  As
+          // eight conditional loads the compiler waited for each in turn
+          // (vmcnt(0) in every branch): the last pass took 8.8 ms for 6.7.
+          e[i] = load_elem_nt(in + tb + (li < nvalid ? li : nvalid - 1));
+          if (li >= nvalid) e[i] = RIn{};
+        } else {
+          e[i] = RG == 2 || li < nvalid ? load_elem_nt(in + tb + li) : RIn{};
+        }
+        if (!PIN && POUT) vhi |= (uint32_t)(rec_val(e[i]) >> 32);
       }
       if (RG == 2) {
         __builtin_amdgcn_sched_barrier(0);
@@ -1272,7 +1327,7 @@ __device__ __forceinline__ void onesweep_body(
 #pragma unroll
     for (int i = 0; i < IPT; ++i) {
       const bool valid = wbase + i * 64 < nvalid;
-      const uint32_t d = (uint32_t)(e[i].key >> shift) & (kBuckets - 1);
+      const uint32_t d = (uint32_t)(rec_key(e[i]) >> shift) & (kBuckets - 1);
       const uint64_t mt = match_digit8(d, __ballot(valid));
       const uint32_t below = mbcnt(mt);
       const uint32_t pre = wcnt[w][d];
@@ -1280,8 +1335,8 @@ __device__ __forceinline__ void onesweep_body(
       if (valid && below == 0) wcnt[w][d] = (WC)(pre + (uint32_t)__popcll(mt));
       if (C16) {
         const int li = wbase + i * 64;
-        if (li == 0) tile_lo[0] = (uint32_t)(e[i].key >> shift16) & 0xFFu;
-        if (li == nvalid - 1) tile_lo[1] = (uint32_t)(e[i].key >> shift16) & 0xFFu;
+        if (li == 0) tile_lo[0] = (uint32_t)(rec_key(e[i]) >> shift16) & 0xFFu;
+        if (li == nvalid - 1) tile_lo[1] = (uint32_t)(rec_key(e[i]) >> shift16) & 0xFFu;
       }
     }
     __syncthreads();
@@ -1329,12 +1384,16 @@ __device__ __forceinline__ void onesweep_body(
 #pragma unroll
       for (int i = 0; i < IPT; ++i) {
         if (wbase + i * 64 < nvalid) {
-          const uint32_t d = (uint32_t)(e[i].key >> shift) & (kBuckets - 1);
-          if (HALVES == 1) {
-            stage[wcnt[w][d] + rk[i]] = e[i];
+          const uint32_t d = (uint32_t)(rec_key(e[i]) >> shift) & (kBuckets - 1);
+          if (POUT) {
+            const uint32_t p = wcnt[w][d] + rk[i];
+            skey[p] = rec_key(e[i]);
+            sval[p] = (uint32_t)rec_val(e[i]);
+          } else if (HALVES == 1) {
+            stage[wcnt[w][d] + rk[i]] = make_rec<Elem>(rec_key(e[i]), rec_val(e[i]));
           } else {
             if (h == 0) rk[i] += wcnt[w][d];
-            if ((int)(rk[i] / HT) == h) stage[rk[i] - h * HT] = e[i];
+            if ((int)(rk[i] / HT) == h) stage[rk[i] - h * HT] = make_rec<Elem>(rec_key(e[i]), rec_val(e[i]));
           }
         }
       }
@@ -1422,7 +1481,7 @@ __device__ __forceinline__ void onesweep_body(
     // emit: one staged record (tile position j, output slot delta + pos) to
     // memory, and its next digit to the sub-array histogram.
     // g = delta[digit] + the record's slot in its run, c = cut[digit].
-    auto emit = [&](auto skew_tag, const Elem& v, int j, int64_t g, uint32_t c) {
+    auto emit = [&](auto skew_tag, const ROut& v, int j, int64_t g, uint32_t c) {
       constexpr bool kSkew = decltype(skew_tag)::value;
       LSB_DASSERT(g >= 0 && g < mcap);
       // In range by construction.  The clamp keeps a look-back that gave up
@@ -1432,7 +1491,7 @@ __device__ __forceinline__ void onesweep_body(
       store_elem(out + gs, v);
       if (NEXT) {
         const uint32_t xs = (uint32_t)j >= (c & 0xFFFFu) ? (c >> 24) : ((c >> 16) & 0xFFu);
-        const uint32_t dn = (uint32_t)(v.key >> next_shift) & (kBuckets - 1);
+        const uint32_t dn = (uint32_t)(rec_key(v) >> next_shift) & (kBuckets - 1);
         const uint32_t slot = xs * kBuckets + dn;
         if (kSkew) {
           // One add per run of equal slots within the wave-instruction: the
@@ -1559,30 +1618,41 @@ __device__ __forceinline__ void onesweep_body(
         constexpr int G = SEG && LSB_SEG_BATCH > 0 && LSB_SEG_BATCH < HT / BLOCK ? LSB_SEG_BATCH : HT / BLOCK;
 #pragma unroll
         for (int k0 = 0; k0 < HT / BLOCK; k0 += G) {
-          Elem v[G];
+          ROut v[G];
           int64_t dl[G];
           uint32_t ct[G];
+          if constexpr (POUT) {
+            uint64_t kk[G];
 #pragma unroll
-          for (int k = 0; k < G; ++k) v[k] = stage[(k0 + k) * BLOCK + t];
+            for (int k = 0; k < G; ++k) kk[k] = skey[(k0 + k) * BLOCK + t];
+#pragma unroll
+            for (int k = 0; k < G; ++k) v[k] = make_rec<Packed>(kk[k], sval[(k0 + k) * BLOCK + t]);
+          } else {
+#pragma unroll
+            for (int k = 0; k < G; ++k) v[k] = stage[(k0 + k) * BLOCK + t];
+          }
 #pragma unroll
           for (int k = 0; k < G; ++k) {
-            const uint32_t d = (uint32_t)(v[k].key >> shift) & (kBuckets - 1);
+            const uint32_t d = (uint32_t)(rec_key(v[k]) >> shift) & (kBuckets - 1);
             dl[k] = delta[d];
             ct[k] = NEXT ? cut[d] : 0u;
           }
 #pragma unroll
           for (int k = 0; k < G; ++k) {
             const int j = (k0 + k) * BLOCK + t;
-            emit(skew_tag, v[k], j, dl[k] + (SEG ? seg_pos(v[k], j, jend) : j), ct[k]);
+            if constexpr (SEG) emit(skew_tag, v[k], j, dl[k] + seg_pos(v[k], j, jend), ct[k]);
+            else emit(skew_tag, v[k], j, dl[k] + j, ct[k]);
           }
         }
         return;
       }
       for (int j = h * HT + t; j < jend; j += BLOCK) {
-        const Elem v = stage[j - h * HT];
+        ROut v;
+        if constexpr (POUT) v = make_rec<Packed>(skey[j], sval[j]);
+        else v = stage[j - h * HT];
         int pos = j;
-        if (SEG) pos = seg_pos(v, j, jend);
-        const uint32_t d = (uint32_t)(v.key >> shift) & (kBuckets - 1);
+        if constexpr (SEG) pos = seg_pos(v, j, jend);
+        const uint32_t d = (uint32_t)(rec_key(v) >> shift) & (kBuckets - 1);
         emit(skew_tag, v, j, delta[d] + pos, NEXT ? cut[d] : 0u);
         if (C16 && mixed16) {
           // The tile crosses a low-byte boundary: its 16-bit digit counts by
@@ -1592,7 +1662,7 @@ __device__ __forceinline__ void onesweep_body(
           // key's run kept its workgroup, and the tile it had already
           // reserved, for the length of the walk).  Active lanes are a
           // prefix, as in emit's skewed count.
-          const uint32_t s16 = (d << 8) | ((uint32_t)(v.key >> shift16) & 0xFFu);
+          const uint32_t s16 = (d << 8) | ((uint32_t)(rec_key(v) >> shift16) & 0xFFu);
           const uint64_t act = __ballot(1);
           const uint32_t prev = (uint32_t)__builtin_amdgcn_update_dpp((int)~s16, (int)s16, 0x138, 0xf, 0xf, false);
           const bool head = prev != s16;
@@ -1628,18 +1698,22 @@ __device__ __forceinline__ void onesweep_body(
       if (nh[i]) atomicAdd(&next_hist[i], nh[i]);
   }
   if (RG == 1 && bkt && cur_sub >= 0 && racc) atomicAdd(&rg.counts[t * kSub + cur_sub], racc);
+  // A value that the packed record cut short: the output is invalid (the
+  // runtime redoes the sort from the kept input with whole records).
+  if (!PIN && POUT && __ballot(vhi != 0) != 0 && lane == 0) atomicOr(rg.wide, 1u);
 }
 
-template <int BLOCK, int IPT, bool NEXT, bool C16, int HALVES, bool SEG = false, bool GATHER = false, int RG = 0>
+template <int BLOCK, int IPT, bool NEXT, bool C16, int HALVES, bool SEG = false, bool GATHER = false, int RG = 0,
+          bool PIN = false, bool POUT = false>
 __global__ __launch_bounds__(BLOCK, (HALVES == 1 ? 2 : 3) * BLOCK / 256) void k_onesweep(
     const Elem* __restrict__ in, Elem* __restrict__ out, int64_t m, int shift, int next_shift,
     const uint32_t* __restrict__ sub_hist, uint32_t* __restrict__ next_hist,
     uint32_t* __restrict__ status, uint32_t* __restrict__ tile_ctr, uint32_t epoch,
     uint32_t* __restrict__ err, uint64_t* __restrict__ totals,
     unsigned long long* __restrict__ count16, SegPass seg, GatherSrc gs, RegionPass rg) {
-  onesweep_body<BLOCK, IPT, NEXT, C16, HALVES, SEG, GATHER, RG>(in, out, m, shift, next_shift, sub_hist,
-                                                                next_hist, status, tile_ctr, epoch, err, totals,
-                                                                count16, seg, gs, rg);
+  onesweep_body<BLOCK, IPT, NEXT, C16, HALVES, SEG, GATHER, RG, PIN, POUT>(in, out, m, shift, next_shift, sub_hist,
+                                                                           next_hist, status, tile_ctr, epoch, err,
+                                                                           totals, count16, seg, gs, rg);
 }
 
 // The placement probe's pass (lsb_context.cpp alloc_records): the same code
@@ -1652,9 +1726,9 @@ __global__ __launch_bounds__(kOsBlock, 2 * kOsBlock / 256) void k_onesweep_probe
     uint32_t* __restrict__ status, uint32_t* __restrict__ tile_ctr, uint32_t epoch,
     uint32_t* __restrict__ err, uint64_t* __restrict__ totals,
     unsigned long long* __restrict__ count16, SegPass seg, GatherSrc gs) {
-  onesweep_body<kOsBlock, kOsIpt, true, false, 1, false, false, 0>(in, out, m, shift, next_shift, sub_hist,
-                                                                   next_hist, status, tile_ctr, epoch, err,
-                                                                   totals, count16, seg, gs, RegionPass());
+  onesweep_body<kOsBlock, kOsIpt, true, false, 1, false, false, 0, false, false>(
+      in, out, m, shift, next_shift, sub_hist, next_hist, status, tile_ctr, epoch, err, totals, count16, seg, gs,
+      RegionPass());
 }
 
 // ------------------------------------------------------------------- place
@@ -2155,6 +2229,16 @@ __global__ __launch_bounds__(256) void k_copy_records(Elem* __restrict__ dst, co
     store_elem(dst + i, load_elem_nt(src + i));
 }
 
+// Packed records back to whole ones (a packed sort that failed part-way:
+// lsb_passes.cpp), streaming.
+__global__ __launch_bounds__(256) void k_unpack(Elem* __restrict__ dst, const Packed* __restrict__ src, int64_t cnt) {
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < cnt; i += stride) {
+    const Packed p = load_elem_nt(src + i);
+    store_elem(dst + i, Elem{rec_key(p), rec_val(p)});
+  }
+}
+
 // ------------------------------------------------------------------ checks
 __global__ __launch_bounds__(256) void k_verify(const Elem* __restrict__ A, int64_t here,
                                                 int64_t gbase, int64_t n, int64_t per, KeyGen gen,
@@ -2320,15 +2404,17 @@ hipError_t launch_count16_chunks(const Elem* B, int64_t m, int shift16, const ui
   return hipGetLastError();
 }
 
-hipError_t launch_sample(const Elem* A, int64_t m, int shift, uint32_t* hist, uint64_t* span, hipStream_t s) {
-  if (shift < 0 || shift > 56) return hipErrorInvalidValue;
+hipError_t launch_sample(const Elem* A, int64_t m, int shift, uint32_t* hist, uint64_t* span, uint32_t* wide,
+                         hipStream_t s) {
+  if (shift < 0 || shift > 56 || !wide) return hipErrorInvalidValue;
   hipError_t e = hipMemsetAsync(hist, 0, sizeof(uint32_t) * kBuckets, s);
   if (e == hipSuccess) e = hipMemsetAsync(span, 0, 2 * sizeof(uint64_t), s);
+  if (e == hipSuccess) e = hipMemsetAsync(wide, 0, sizeof(uint32_t), s);
   if (e != hipSuccess || m <= 0) return e;
   const int64_t TT = (m + kTile - 1) / kTile;
   const unsigned g = (unsigned)(TT < kSampleTiles ? TT : kSampleTiles);
   hipLaunchKernelGGL(k_sample, dim3(g), dim3(kSampleBlock), 0, s, A, m, shift, hist,
-                     reinterpret_cast<unsigned long long*>(span));
+                     reinterpret_cast<unsigned long long*>(span), wide);
   return hipGetLastError();
 }
 
@@ -2386,6 +2472,11 @@ hipError_t launch_onesweep(const Elem* in, Elem* out, int64_t m, int shift, int 
     // (rm = 2): whole stage, no 16-bit counts, totals, segments or gathering.
     if (c16 || extra.halves != 1 || extra.seg || gat || extra.probe || extra.totals) return hipErrorInvalidValue;
     if (rm == 1 && (next_shift < 0 || !rp.ovf)) return hipErrorInvalidValue;
+    // Packed records: the first pass packs (and reports wide values), the
+    // pass that reads its layout carries them on to a next-counting pass.
+    if (rm == 1 ? (extra.pack_in || (extra.pack_out && !rp.wide))
+                : (extra.pack_in != extra.pack_out || (extra.pack_in && next_shift < 0)))
+      return hipErrorInvalidValue;
     if (next_shift >= 0) {
       e = hipMemsetAsync(next_hist, 0, sizeof(uint32_t) * kSub * kBuckets, s);
       if (e != hipSuccess) return e;
@@ -2393,10 +2484,20 @@ hipError_t launch_onesweep(const Elem* in, Elem* out, int64_t m, int shift, int 
     if (rm == 1) {
       e = hipMemsetAsync(rp.counts, 0, sizeof(uint32_t) * kRegions, s);
       if (e == hipSuccess) e = hipMemsetAsync(rp.ovf, 0, sizeof(uint32_t), s);
+      if (e == hipSuccess && extra.pack_out) e = hipMemsetAsync(rp.wide, 0, sizeof(uint32_t), s);
       if (e != hipSuccess) return e;
-      hipLaunchKernelGGL((k_onesweep<kOsBlock, kOsIpt, true, false, 1, false, false, 1>), gd, bd, 0, s, in, out,
-                         m, shift, next_shift, sub_hist, next_hist, st, tile_ctr, epoch, err, nullptr, nullptr,
-                         SegPass(), gsrc, rp);
+      if (extra.pack_out)
+        hipLaunchKernelGGL((k_onesweep<kOsBlock, kOsIpt, true, false, 1, false, false, 1, false, true>), gd, bd, 0, s,
+                           in, out, m, shift, next_shift, sub_hist, next_hist, st, tile_ctr, epoch, err, nullptr,
+                           nullptr, SegPass(), gsrc, rp);
+      else
+        hipLaunchKernelGGL((k_onesweep<kOsBlock, kOsIpt, true, false, 1, false, false, 1>), gd, bd, 0, s, in, out,
+                           m, shift, next_shift, sub_hist, next_hist, st, tile_ctr, epoch, err, nullptr, nullptr,
+                           SegPass(), gsrc, rp);
+    } else if (next_shift >= 0 && extra.pack_in) {
+      hipLaunchKernelGGL((k_onesweep<kOsBlock, kOsIpt, true, false, 1, false, false, 2, true, true>), gd, bd, 0, s,
+                         in, out, m, shift, next_shift, sub_hist, next_hist, st, tile_ctr, epoch, err, nullptr,
+                         nullptr, SegPass(), gsrc, rp);
     } else if (next_shift >= 0) {
       hipLaunchKernelGGL((k_onesweep<kOsBlock, kOsIpt, true, false, 1, false, false, 2>), gd, bd, 0, s, in, out,
                          m, shift, next_shift, sub_hist, next_hist, st, tile_ctr, epoch, err, nullptr, nullptr,
@@ -2406,6 +2507,25 @@ hipError_t launch_onesweep(const Elem* in, Elem* out, int64_t m, int shift, int 
                          m, shift, 0, sub_hist, nullptr, st, tile_ctr, epoch, err, nullptr, nullptr, SegPass(),
                          gsrc, rp);
     }
+  } else if (extra.pack_in) {
+    // A later pass of a packed sort: Packed -> Packed counting the next
+    // digit, or the last pass Packed -> Elem.  Whole stage, nothing else.
+    if (c16 || extra.halves != 1 || extra.seg || gat || extra.probe || extra.totals ||
+        extra.pack_out != (next_shift >= 0))
+      return hipErrorInvalidValue;
+    if (next_shift >= 0) {
+      e = hipMemsetAsync(next_hist, 0, sizeof(uint32_t) * kSub * kBuckets, s);
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL((k_onesweep<kOsBlock, kOsIpt, true, false, 1, false, false, 0, true, true>), gd, bd, 0, s,
+                         in, out, m, shift, next_shift, sub_hist, next_hist, st, tile_ctr, epoch, err, nullptr,
+                         nullptr, SegPass(), gsrc, RegionPass());
+    } else {
+      hipLaunchKernelGGL((k_onesweep<kOsBlock, kOsIpt, false, false, 1, false, false, 0, true, false>), gd, bd, 0, s,
+                         in, out, m, shift, 0, sub_hist, nullptr, st, tile_ctr, epoch, err, nullptr, nullptr,
+                         SegPass(), gsrc, RegionPass());
+    }
+  } else if (extra.pack_out) {
+    return hipErrorInvalidValue;  // only the regional first pass packs
   } else if (extra.probe) {
     // The placement probe: a pass counting the next digit (the sort's usual
     // instance), whole stage, under its own name.
@@ -2562,6 +2682,12 @@ hipError_t launch_gather_desc(const GatherSrc& g, int64_t m, TileDesc* desc, hip
 hipError_t launch_copy_records(Elem* dst, const Elem* src, int64_t cnt, hipStream_t s) {
   if (cnt <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_copy_records, dim3(grid_for(cnt, 256, 8192)), dim3(256), 0, s, dst, src, cnt);
+  return hipGetLastError();
+}
+
+hipError_t launch_unpack(Elem* dst, const Packed* src, int64_t cnt, hipStream_t s) {
+  if (cnt <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_unpack, dim3(grid_for(cnt, 256, 8192)), dim3(256), 0, s, dst, src, cnt);
   return hipGetLastError();
 }
 

@@ -79,9 +79,11 @@ bool onesweep_applies(const lsb_ctx* c) {
 
 // The regional first pass's rg_buf words (region_sample, region_first): [kRgCounts, +2048) region counts, [kRgHist, +256) the
 // sample's digit counts, kRgOvf the overflow word, [kRgSpan, +4) the
-// sample's span (2 u64).
-constexpr int kRgCounts = 0, kRgHist = lsb::kRegions, kRgOvf = kRgHist + lsb::kBuckets,
-              kRgSpan = kRgOvf + 2, kRgWords = kRgSpan + 4;
+// sample's span (2 u64).  Packed records (LSB_OPT_PACK_VALUES): kRgWide, beside
+// the overflow word and read back with it, is set by the packing first pass
+// when a value needs more than 32 bits; kRgSampleWide by the sample.
+constexpr int kRgCounts = 0, kRgHist = lsb::kRegions, kRgOvf = kRgHist + lsb::kBuckets, kRgWide = kRgOvf + 1,
+              kRgSpan = kRgOvf + 2, kRgSampleWide = kRgSpan + 4, kRgWords = kRgSampleWide + 1;
 
 int onesweep_ensure(Rank& r) {
   if (r.os_status) return LSB_OK;
@@ -207,8 +209,14 @@ std::vector<int> varying_bytes(uint64_t varying) {
 // From digits[from] on; rp: digits[from]'s pass reads the regional layout
 // (its input's histogram in os_hist[from & 1]).
 // *disarm (when given) turns false once pass `from` is queued.
+// packed: r.A holds Packed records (the first pass packed them); every pass
+// but the last writes them again, the last writes whole records.  Once pass
+// `from` is queued the input no longer covers an error return (*disarm), so
+// a pass that then fails to launch leaves r.A unpacked (k_unpack into r.B,
+// then the swap): whole records, a permutation of the input.  If even that
+// cannot be queued the context refuses further sorts (lsb_ctx::broken).
 int onesweep_digits(lsb_ctx* c, Rank& r, const std::vector<int>& digits, int* passes, size_t from = 0,
-                    const lsb::RegionPass* rp = nullptr, bool* disarm = nullptr) {
+                    const lsb::RegionPass* rp = nullptr, bool* disarm = nullptr, bool packed = false) {
   uint32_t* hist[2] = {r.os_hist, r.os_hist + lsb::kOnesweepSubs * lsb::kBuckets};
   for (size_t i = from; i < digits.size(); ++i) {
     const int shift = digits[i] * lsb::kDigitBits;
@@ -220,7 +228,22 @@ int onesweep_digits(lsb_ctx* c, Rank& r, const std::vector<int>& digits, int* pa
       x.region = rp;
       x.region_mode = 2;
     }
-    LSB_TRY(onesweep_launch(c, r, shift, next, hist[i & 1], hist[(i + 1) & 1], x));
+    x.pack_in = packed;
+    x.pack_out = packed && next >= 0;
+    const int rc = onesweep_launch(c, r, shift, next, hist[i & 1], hist[(i + 1) & 1], x);
+    if (rc != LSB_OK) {
+      if (packed && i > from) {
+        const hipError_t e =
+            lsb::launch_unpack(r.B, reinterpret_cast<const lsb::Packed*>(r.A), r.here, r.stream);
+        if (e == hipSuccess) {
+          std::swap(r.A, r.B);
+        } else {
+          (void)hipGetLastError();
+          c->broken = true;
+        }
+      }
+      return rc;
+    }
     ++*passes;
     if (disarm) *disarm = false;
   }
@@ -256,6 +279,7 @@ lsb::RegionPass region_pass(Rank& r) {
   rp.cap = r.rg_cap;
   rp.counts = r.rg_buf + kRgCounts;
   rp.ovf = r.rg_buf + kRgOvf;
+  rp.wide = r.rg_buf + kRgWide;
   return rp;
 }
 
@@ -267,7 +291,7 @@ int region_sample(lsb_ctx* c, Rank& r, int byte, bool* go, uint64_t* seen) {
   {
     Timer t(c, &r, LSB_K_UPSWEEP);
     HIP_TRY(lsb::launch_sample(r.A, r.here, byte * lsb::kDigitBits, r.rg_buf + kRgHist,
-                               reinterpret_cast<uint64_t*>(r.rg_buf + kRgSpan), r.stream));
+                               reinterpret_cast<uint64_t*>(r.rg_buf + kRgSpan), r.rg_buf + kRgSampleWide, r.stream));
   }
   HIP_TRY(hipMemcpyAsync(r.rg_h + kRgHist, r.rg_buf + kRgHist, (size_t)(kRgWords - kRgHist) * sizeof(uint32_t),
                          hipMemcpyDeviceToHost, r.stream));
@@ -299,16 +323,20 @@ int region_sample(lsb_ctx* c, Rank& r, int byte, bool* go, uint64_t* seen) {
 
 // The first pass into the regional layout (r.A -> r.B, then they swap) on
 // the byte at `shift`, counting the byte at next_shift into os_hist[1]; the
-// overflow word's read-back is queued.
-int region_first(lsb_ctx* c, Rank& r, int shift, int next_shift, int* passes) {
+// overflow word's read-back is queued.  pack: the layout holds Packed
+// records, and the wide word is read back in the same copy.
+int region_first(lsb_ctx* c, Rank& r, int shift, int next_shift, int* passes, bool pack = false) {
   const lsb::RegionPass rp = region_pass(r);
   begin_pass(c, shift);
   lsb::OnesweepExtra x;
   x.region = &rp;
   x.region_mode = 1;
+  x.pack_out = pack;
   LSB_TRY(onesweep_launch(c, r, shift, next_shift, nullptr, r.os_hist + lsb::kOnesweepSubs * lsb::kBuckets, x));
   ++*passes;
-  HIP_TRY(hipMemcpyAsync(r.rg_h + kRgOvf, r.rg_buf + kRgOvf, sizeof(uint32_t), hipMemcpyDeviceToHost, r.stream));
+  r.rg_h[kRgWide] = 0;
+  HIP_TRY(hipMemcpyAsync(r.rg_h + kRgOvf, r.rg_buf + kRgOvf, (pack ? 2 : 1) * sizeof(uint32_t),
+                         hipMemcpyDeviceToHost, r.stream));
   return LSB_OK;
 }
 
@@ -372,6 +400,7 @@ struct LocalSort {
   std::vector<int> digits, msd;
   bool fuse = false;
   bool region = false;  // pass 0 ran into the regional layout (region_first)
+  bool pack = false;    // ... as Packed records (LSB_OPT_PACK_VALUES)
   // {A, B, R} stays a permutation of {X0, X1, X2} at every step (the pass
   // loop swaps A and B; R holds X0, the kept input, from the first pass on).
   // While armed, an error return restores A = X0, B = X1, R = X2, so the
@@ -410,6 +439,7 @@ struct LocalSort {
   int hybrid_passes(size_t from);
   int classic();
   int first_hist(int byte, bool* skewed, bool* constant);
+  int restart_counted();
   int queue_err_word() {
     // The look-back's give-up word, read by lsb_sync.
     HIP_TRY(hipMemcpyAsync(r.os_err_h, r.os_ctr + lsb::kOnesweepSubs, sizeof(uint32_t),
@@ -492,7 +522,12 @@ int LocalSort::begin() {
       X1 = r.B;
       X2 = r.R;
       armed = true;
-      return region_first(c, r, 0, lsb::kDigitBits, &passes);
+      // Packed records between the passes when no sampled value needs more
+      // than 32 bits (the first pass checks them all), unless an earlier
+      // sort of this context met one that did.  2 (tests): pack regardless.
+      pack = c->pack_values == 2 ||
+             (c->pack_values == 1 && !c->pack_wide && r.rg_h[kRgSampleWide] == 0);
+      return region_first(c, r, 0, lsb::kDigitBits, &passes, pack);
     }
     varying = ~0ull;
     LSB_TRY(count_byte(c, r, 0, c->skip_constant));
@@ -542,32 +577,21 @@ int LocalSort::queue() {
     region = false;
     HIP_TRY(hipStreamSynchronize(r.stream));
     digits = varying_bytes(~0ull);
-    if (r.rg_h[kRgOvf] == 0) {
+    const bool wide = pack && r.rg_h[kRgWide] != 0;
+    if (wide) c->pack_wide = true;  // option 1: later sorts of this context do not try again
+    if (r.rg_h[kRgOvf] == 0 && !wide) {
       r.os_halves = 1;
       const lsb::RegionPass rp = region_pass(r);
-      LSB_TRY(onesweep_digits(c, r, digits, &passes, 1, &rp, &armed));
+      if (pack) c->last_records = LSB_RECORDS_PACKED;
+      LSB_TRY(onesweep_digits(c, r, digits, &passes, 1, &rp, &armed, pack));
       kind = kDone;
       return queue_err_word();
     }
-    // A region overflowed: start over from the input, kept in place (pass 0
-    // read it and wrote the other buffer), with the usual first read.
-    c->last_first = LSB_FIRST_REGIONAL_REDONE;
-    std::swap(r.A, r.B);
-    armed = false;
-    passes = 0;
-    c->pass_cursor = 0;
-    c->cur_pass = 0;
-    HIP_TRY(hipMemsetAsync(r.span, 0, 2 * sizeof(uint64_t), r.stream));
-    LSB_TRY(count_byte(c, r, 0, c->skip_constant));
-    LSB_TRY(queue_halves(c, r, r.os_hist));
-    HIP_TRY(hipMemcpyAsync(r.span_h, r.span, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, r.stream));
-    HIP_TRY(hipStreamSynchronize(r.stream));
-    varying = c->skip_constant ? r.span_h[0] & r.span_h[1] : ~0ull;
-    digits = varying_bytes(varying);
-    LSB_TRY(choose_halves(c, r, true));
-    LSB_TRY(onesweep_digits(c, r, digits, &passes));
-    kind = kDone;
-    return queue_err_word();
+    // A region overflowed, or a value did not fit its packed record: start
+    // over from the input, kept in place (pass 0 read it and wrote the other
+    // buffer), with the usual first read and whole records.
+    if (wide) c->last_records = LSB_RECORDS_PACKED_REDONE;
+    return restart_counted();
   }
   if (kind == kHybrid && region) {
     region = false;
@@ -627,6 +651,28 @@ int LocalSort::queue() {
     return queue_err_word();
   }
   return hybrid_passes(0);
+}
+
+// The LSD passes again after a regional first pass whose output cannot be
+// used: from the input, with the usual first read.
+int LocalSort::restart_counted() {
+  c->last_first = LSB_FIRST_REGIONAL_REDONE;
+  std::swap(r.A, r.B);
+  armed = false;
+  passes = 0;
+  c->pass_cursor = 0;
+  c->cur_pass = 0;
+  HIP_TRY(hipMemsetAsync(r.span, 0, 2 * sizeof(uint64_t), r.stream));
+  LSB_TRY(count_byte(c, r, 0, c->skip_constant));
+  LSB_TRY(queue_halves(c, r, r.os_hist));
+  HIP_TRY(hipMemcpyAsync(r.span_h, r.span, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, r.stream));
+  HIP_TRY(hipStreamSynchronize(r.stream));
+  varying = c->skip_constant ? r.span_h[0] & r.span_h[1] : ~0ull;
+  digits = varying_bytes(varying);
+  LSB_TRY(choose_halves(c, r, true));
+  LSB_TRY(onesweep_digits(c, r, digits, &passes));
+  kind = kDone;
+  return queue_err_word();
 }
 
 // The k passes: A -> B, then B <-> R; the input X0 is kept.  The last one

@@ -183,6 +183,9 @@ struct lsb_ctx {
   bool gather = true;         // LSB_OPT_EXCHANGE_GATHER: count-only placement + gathered pass
   int os_split = 0;           // LSB_OPT_ONESWEEP_SPLIT: 0 auto, 1 never, 2 always
   int fail_onesweep = 0;      // LSB_OPT_FAIL_ONESWEEP: the n-th k_onesweep launch fails (tests)
+  int pack_values = 1;        // LSB_OPT_PACK_VALUES: 0 never, 1 when the values fit 32 bits, 2 always try
+  bool pack_wide = false;     // a packing first pass of this context met a value over 32 bits
+  bool broken = false;        // a failed packed sort could not restore whole records: no more sorts
   int hybrid = 0;             // LSB_OPT_HYBRID: 0 off, 1 k byte passes (the last one
                               // ordering segments, + k_segfix), 2 the same + a k_segsort pass
   int64_t coll_calls = 0, coll_bytes = 0, coll_max = 0;  // element payload handed to the collective
@@ -191,6 +194,7 @@ struct lsb_ctx {
   int last_exchanges = 0;
   uint64_t last_varying = 0;
   int last_first = 0;  // the first pass's form (lsb_get_first_pass)
+  int last_records = 0;  // the records between the passes (lsb_get_last_records)
   lsb::KeyGen keygen;
   std::vector<lsb_rt::PendingEvent> pending;
   std::vector<std::pair<int, hipEvent_t>> event_pool;  // (device, event) of finished timings

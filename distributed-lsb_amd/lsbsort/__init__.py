@@ -56,6 +56,8 @@ OPT_EXCHANGE_GATHER = 10
 OPT_FAIL_ONESWEEP = 11
 OPT_REGION_FIRST = 12
 OPT_EXCHANGE_CHUNKS = 13
+OPT_PACK_VALUES = 14
+RECORDS_FULL, RECORDS_PACKED, RECORDS_PACKED_REDONE = 0, 1, 2
 FIRST_COUNT, FIRST_REGIONAL, FIRST_REGIONAL_REDONE = 0, 1, 2
 MAX_PASSES = 16
 
@@ -160,6 +162,7 @@ def _lib() -> ctypes.CDLL:
             "lsb_set_option": (i32, [vp, i32, i64]),
             "lsb_get_last_sort": (i32, [vp, vp, vp, vp]),
             "lsb_get_first_pass": (i32, [vp, vp]),
+            "lsb_get_last_records": (i32, [vp, vp]),
             "lsb_local_ranks": (i32, [vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
             "lsb_generate": (i32, [vp]),
             "lsb_generate_ex": (i32, [vp, i32, ctypes.c_double]),
@@ -493,6 +496,14 @@ class World:
         FIRST_REGIONAL or FIRST_REGIONAL_REDONE."""
         f = ctypes.c_int()
         _check(_lib().lsb_get_first_pass(self._h, ctypes.byref(f)), "lsb_get_first_pass")
+        return int(f.value)
+
+    def last_records(self) -> int:
+        """The records the last my_sort's passes handed each other
+        (lsb_get_last_records): RECORDS_FULL, RECORDS_PACKED or
+        RECORDS_PACKED_REDONE."""
+        f = ctypes.c_int()
+        _check(_lib().lsb_get_last_records(self._h, ctypes.byref(f)), "lsb_get_last_records")
         return int(f.value)
 
     def kernel_stats(self) -> dict:

@@ -161,6 +161,21 @@ typedef struct lsb_ctx lsb_ctx_t;
                                       environment's LSB_EXCHANGE_CHUNKS sets a context's start
                                       value) sends after the whole pass.  Same output. */
 
+#define LSB_OPT_PACK_VALUES     14 /* P == 1 LSD sorts that start with the regional pass
+                                      (LSB_OPT_REGION_FIRST): 1 (default) when no value of the
+                                      2^20-record sample needs more than 32 bits (the reference's
+                                      values are global indices), the passes hand each other
+                                      12-byte records {key, low word of the value}: the first
+                                      pass packs, the last writes 16-byte records again, and the
+                                      sort moves 200 instead of 256 bytes per record.  The first
+                                      pass checks every value; one that does not fit makes the
+                                      sort start over from its input with whole records, and
+                                      later sorts of the context do not try again.  0: never
+                                      pack.  2 (tests): pack without consulting the sample or
+                                      earlier sorts.  Same output (lsb_get_last_records says
+                                      which form ran).  The environment's LSB_PACK_VALUES sets
+                                      a context's start value. */
+
 /* ---- geometry: DistributedArray::create (mpi/mpi_lsbsort.cpp:144-149) ---- */
 int64_t lsb_per_rank(int64_t n_total, int num_ranks);            /* ceil(n/P) */
 int64_t lsb_here(int64_t n_total, int num_ranks, int rank);      /* clamp(n - r*per, 0, per) */
@@ -267,6 +282,18 @@ int  lsb_get_last_sort(lsb_ctx_t* ctx, int* local_passes, int* exchanges,
 #define LSB_FIRST_REGIONAL        1
 #define LSB_FIRST_REGIONAL_REDONE 2
 int  lsb_get_first_pass(lsb_ctx_t* ctx, int* form);
+/* The records the last lsb_sort's passes handed each other
+ * (LSB_OPT_PACK_VALUES): LSB_RECORDS_FULL 16-byte records throughout;
+ * LSB_RECORDS_PACKED 12-byte records between the first and the last pass;
+ * LSB_RECORDS_PACKED_REDONE the first pass packed, met a value over 32 bits,
+ * and the sort started over from its input with 16-byte records.
+ * If a pass of a packed sort fails to launch, lsb_sort leaves whole records
+ * (a permutation of the input) in A as after any error; should even that
+ * fail, lsb_sort returns LSB_ERR_STATE until lsb_generate loads A again. */
+#define LSB_RECORDS_FULL          0
+#define LSB_RECORDS_PACKED        1
+#define LSB_RECORDS_PACKED_REDONE 2
+int  lsb_get_last_records(lsb_ctx_t* ctx, int* form);
 /* == globalShuffle(A, B, digit): one pass, result in A. */
 int  lsb_pass(lsb_ctx_t* ctx, int digit);
 int  lsb_sync(lsb_ctx_t* ctx);
