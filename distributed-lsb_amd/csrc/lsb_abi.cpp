@@ -1,5 +1,6 @@
 // The C ABI (include/lsb.h): entry points over the runtime (lsb_rt.h) and the
 // pure host planners.
+#include "lsb_keyform.h"
 #include "lsb_rt.h"
 
 using namespace lsb_rt;
@@ -334,6 +335,86 @@ int lsb_copy_out(lsb_ctx_t* c, int rank, int64_t off, int64_t cnt, lsb_elem_t* h
   HIP_TRY(hipSetDevice(r->dev));
   HIP_TRY(hipStreamSynchronize(r->stream));
   HIP_TRY(hipMemcpy(host, r->A + off, (size_t)cnt * sizeof(Elem), hipMemcpyDeviceToHost));
+  return LSB_OK;
+}
+
+uint64_t lsb_key_encode(uint64_t bits, int key_type, int flags) { return lsb::encode(bits, key_type, flags); }
+
+uint64_t lsb_key_decode(uint64_t key, int key_type, int flags) { return lsb::decode(key, key_type, flags); }
+
+namespace {
+
+// A caller's column of cnt elements of `elem` bytes at p, before a kernel may
+// touch it: aligned to its element, device (or managed) memory of the rank's
+// device as the runtime knows it, and [p, p + cnt * elem) inside the
+// allocation that holds p.  A pageable host pointer fails the second test.
+int check_column(const Rank& r, const void* p, size_t elem, int64_t cnt, const char* where) {
+  if (reinterpret_cast<uintptr_t>(p) % elem != 0) return fail(LSB_ERR_INVALID, where, "column not aligned to its element");
+  hipPointerAttribute_t at;
+  memset(&at, 0, sizeof at);
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(LSB_ERR_INVALID, where, "column is not device memory");
+  }
+  if ((at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged) || at.device != r.dev)
+    return fail(LSB_ERR_INVALID, where, "column is not device memory of the rank's device");
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(LSB_ERR_INVALID, where, "column's allocation unknown");
+  }
+  const uintptr_t lo = reinterpret_cast<uintptr_t>(base), at_p = reinterpret_cast<uintptr_t>(p);
+  if (at_p < lo || at_p - lo > size || (uint64_t)cnt > (size - (at_p - lo)) / elem)
+    return fail(LSB_ERR_INVALID, where, "column range leaves its allocation");
+  return LSB_OK;
+}
+
+// The checks lsb_load_columns and lsb_store_columns share; all of them come
+// before the first launch.  *rank_out: the rank, once every check has passed.
+int check_columns(lsb_ctx* c, int rank, int64_t off, int64_t cnt, const void* keys, int key_type,
+                  const void* vals, int val_bytes, int flags, const char* where, Rank** rank_out) {
+  LSB_TRY(check_ctx(c));
+  Rank* r = local_rank(c, rank);
+  if (!r || off < 0 || cnt < 0 || off > c->per || cnt > c->per - off)
+    return fail(LSB_ERR_INVALID, where, "rank or range");
+  if (!lsb::key_form_valid(key_type, flags)) return fail(LSB_ERR_INVALID, where, "key type or flags");
+  if (val_bytes != 0 && val_bytes != 4 && val_bytes != 8) return fail(LSB_ERR_INVALID, where, "val_bytes");
+  if ((val_bytes == 0) != (vals == nullptr)) return fail(LSB_ERR_INVALID, where, "val_bytes and values disagree");
+  *rank_out = r;
+  if (cnt == 0) return LSB_OK;
+  HIP_TRY(hipSetDevice(r->dev));
+  if (keys) LSB_TRY(check_column(*r, keys, (size_t)lsb::key_bytes(key_type), cnt, where));
+  if (vals) LSB_TRY(check_column(*r, vals, (size_t)val_bytes, cnt, where));
+  return LSB_OK;
+}
+
+}  // namespace
+
+int lsb_load_columns(lsb_ctx_t* c, int rank, int64_t off, int64_t cnt, const void* keys_dev, int key_type,
+                     const void* vals_dev, int val_bytes, int flags) {
+  Rank* r = nullptr;
+  LSB_TRY(check_columns(c, rank, off, cnt, keys_dev, key_type, vals_dev, val_bytes, flags, "lsb_load_columns", &r));
+  if (cnt == 0) return LSB_OK;
+  if (!keys_dev) return fail(LSB_ERR_INVALID, "lsb_load_columns", "null keys");
+  HIP_TRY(hipStreamSynchronize(r->stream));
+  // The value of a record without one: its global index (mpi/mpi_lsbsort.cpp:650-656).
+  const uint64_t val0 = (uint64_t)r->rank * (uint64_t)c->per + (uint64_t)off;
+  HIP_TRY(lsb::launch_load_columns(r->A + off, cnt, keys_dev, key_type, vals_dev, val_bytes, val0, flags,
+                                   r->stream));
+  HIP_TRY(hipStreamSynchronize(r->stream));
+  return LSB_OK;
+}
+
+int lsb_store_columns(lsb_ctx_t* c, int rank, int64_t off, int64_t cnt, void* keys_dev, int key_type,
+                      void* vals_dev, int val_bytes, int flags) {
+  Rank* r = nullptr;
+  LSB_TRY(check_columns(c, rank, off, cnt, keys_dev, key_type, vals_dev, val_bytes, flags, "lsb_store_columns", &r));
+  if (!keys_dev && !vals_dev) return fail(LSB_ERR_INVALID, "lsb_store_columns", "no output column");
+  if (cnt == 0) return LSB_OK;
+  HIP_TRY(hipStreamSynchronize(r->stream));
+  HIP_TRY(lsb::launch_store_columns(r->A + off, cnt, keys_dev, key_type, vals_dev, val_bytes, flags, r->stream));
+  HIP_TRY(hipStreamSynchronize(r->stream));
   return LSB_OK;
 }
 

@@ -403,6 +403,17 @@ hipError_t launch_merge_level(const MergeLevel& level, int64_t* path, int grid, 
 hipError_t launch_copy_records(Elem* dst, const Elem* src, int64_t cnt, hipStream_t s);
 // cnt packed records src -> Elem records dst (distinct buffers).
 hipError_t launch_unpack(Elem* dst, const Packed* src, int64_t cnt, hipStream_t s);
+// Caller-owned columns (lsb_columns.hip; key forms: lsb_keyform.h).  Load:
+// A[i] = {encode(keys[i]), vals[i]} for i in [0, cnt), the value 8 bytes raw,
+// 4 bytes zero-extended, or val0 + i when val_bytes is 0 (vals null exactly
+// then).  Store: the inverse, keys[i] = decode(A[i].key), vals[i] = the value
+// or its low word; keys or vals may be null.  Columns are aligned to their
+// element; 16-byte aligned ones take 16-byte accesses.  hipErrorInvalidValue
+// on an unknown key type, flag or val_bytes, before any launch.
+hipError_t launch_load_columns(Elem* A, int64_t cnt, const void* keys, int key_type, const void* vals,
+                               int val_bytes, uint64_t val0, int flags, hipStream_t s);
+hipError_t launch_store_columns(const Elem* A, int64_t cnt, void* keys, int key_type, void* vals, int val_bytes,
+                                int flags, hipStream_t s);
 hipError_t launch_verify(const Elem* A, int64_t here, int64_t gbase, int64_t n, int64_t per,
                          KeyGen gen, unsigned long long* first_bad, hipStream_t s);
 

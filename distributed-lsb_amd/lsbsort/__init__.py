@@ -17,6 +17,13 @@ seams so tests read like the reference program:
   A.print(10) (:171-200)      ``World.print_lines("A", 10)``
   ==========================  ==============================================
 
+A caller that holds keys and values on the GPU (1-D torch CUDA tensors; typed
+keys, either order, values or argsort) uses ``sort(keys, values)``, or
+``World.load_columns`` / ``World.store_columns`` around ``my_sort()``.  torch
+is imported only inside those functions.  A process that uses them imports
+torch before the first call into this module: the library then binds to the
+HIP runtime torch brought, and both see the same device memory.
+
 Errors from the library raise :class:`LsbError` (the reference aborts on
 MPI errors, mpi/mpi_lsbsort.cpp:17-19).  There is no CPU fallback: if the
 HIP library is missing or no GPU is present, calls fail loudly.
@@ -60,6 +67,9 @@ OPT_PACK_VALUES = 14
 RECORDS_FULL, RECORDS_PACKED, RECORDS_PACKED_REDONE = 0, 1, 2
 FIRST_COUNT, FIRST_REGIONAL, FIRST_REGIONAL_REDONE = 0, 1, 2
 MAX_PASSES = 16
+# Key forms of caller-owned columns (LSB_KEY_*, LSB_ORDER_DESCENDING).
+KEY_U64, KEY_I64, KEY_F64, KEY_U32, KEY_I32, KEY_F32 = range(6)
+ORDER_DESCENDING = 1
 
 
 class LsbError(RuntimeError):
@@ -168,6 +178,10 @@ def _lib() -> ctypes.CDLL:
             "lsb_generate_ex": (i32, [vp, i32, ctypes.c_double]),
             "lsb_copy_in": (i32, [vp, i32, i64, i64, vp]),
             "lsb_copy_out": (i32, [vp, i32, i64, i64, vp]),
+            "lsb_key_encode": (ctypes.c_uint64, [ctypes.c_uint64, i32, i32]),
+            "lsb_key_decode": (ctypes.c_uint64, [ctypes.c_uint64, i32, i32]),
+            "lsb_load_columns": (i32, [vp, i32, i64, i64, vp, i32, vp, i32, i32]),
+            "lsb_store_columns": (i32, [vp, i32, i64, i64, vp, i32, vp, i32, i32]),
             "lsb_sort": (i32, [vp]),
             "lsb_pass": (i32, [vp, i32]),
             "lsb_sync": (i32, [vp]),
@@ -265,6 +279,90 @@ def source_digest() -> str:
         with open(os.path.join(ROOT_DIR, rel), "rb") as f:
             h.update(f.read())
     return h.hexdigest()
+
+
+def key_encode(bits: int, key_type: int, descending: bool = False) -> int:
+    """lsb_key_encode: the unsigned 64-bit key the passes sort a typed key's
+    raw bits by (0 on an unknown type).  Host arithmetic only."""
+    return int(_lib().lsb_key_encode(bits, key_type, ORDER_DESCENDING if descending else 0))
+
+
+def key_decode(key: int, key_type: int, descending: bool = False) -> int:
+    """lsb_key_decode: the inverse of key_encode."""
+    return int(_lib().lsb_key_decode(key, key_type, ORDER_DESCENDING if descending else 0))
+
+
+def _key_type_of(t, key_type=None) -> int:
+    """The LSB_KEY_* of a torch tensor's dtype (key_type given: checked
+    against the element size instead, for dtypes torch has no name for)."""
+    import torch
+    if key_type is not None:
+        if key_type not in range(6) or t.element_size() != (4 if key_type >= KEY_U32 else 8):
+            raise ValueError(f"key_type {key_type} does not fit {t.dtype}")
+        return key_type
+    table = {torch.int64: KEY_I64, torch.float64: KEY_F64, torch.int32: KEY_I32, torch.float32: KEY_F32}
+    for name, kt in (("uint64", KEY_U64), ("uint32", KEY_U32)):
+        if hasattr(torch, name):
+            table[getattr(torch, name)] = kt
+    if t.dtype not in table:
+        raise ValueError(f"no key type for {t.dtype}; pass key_type=")
+    return table[t.dtype]
+
+
+def _check_column(t, what: str, device=None):
+    """A column the library can take: a 1-D contiguous CUDA torch tensor of 4-
+    or 8-byte elements (on `device`, when given).  ValueError otherwise."""
+    import torch
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{what}: not a torch tensor")
+    if not t.is_cuda:
+        raise ValueError(f"{what}: not on a GPU")
+    if t.dim() != 1:
+        raise ValueError(f"{what}: not 1-D")
+    if not t.is_contiguous():
+        raise ValueError(f"{what}: not contiguous")
+    if t.element_size() not in (4, 8):
+        raise ValueError(f"{what}: elements of {t.element_size()} bytes")
+    if device is not None and t.device != device:
+        raise ValueError(f"{what}: on {t.device}, not {device}")
+
+
+def sort(keys, values=None, descending: bool = False, ranks: int = 1, radix_bits: int = 8,
+         key_type: Optional[int] = None):
+    """Stable sort of device columns: (sorted_keys, sorted_values), or with
+    values=None (sorted_keys, indices), indices the int64 stable argsort.
+
+    keys: 1-D contiguous CUDA tensor (int64, float64, int32, float32, uint64,
+    uint32; key_type= for other dtypes of 4 or 8 bytes); values: any 4- or
+    8-byte dtype, same length.  Floats sort in the order of lsb.h (NaNs at both
+    ends by sign, -0.0 before +0.0); equal keys keep their input order in both
+    directions.  The inputs are left untouched; the outputs are fresh tensors.
+    One World(n, ranks) on the keys' device does the work, rank r holding block
+    [r * per, r * per + here(r))."""
+    import torch
+    _check_column(keys, "keys")
+    kt = _key_type_of(keys, key_type)
+    if values is not None:
+        _check_column(values, "values", keys.device)
+        if values.numel() != keys.numel():
+            raise ValueError("keys and values differ in length")
+    if ranks < 1:
+        raise ValueError("ranks")
+    n = keys.numel()
+    out_k = torch.empty_like(keys)
+    out_v = torch.empty_like(values) if values is not None else torch.empty(n, dtype=torch.int64, device=keys.device)
+    if n == 0:
+        return out_k, out_v
+    dev = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
+    with World(n, ranks=ranks, devices=[dev] * ranks, radix_bits=radix_bits) as w:
+        blocks = [(r, r * w.per, w.here(r)) for r in range(ranks) if w.here(r)]
+        for r, lo, h in blocks:
+            w.load_columns(r, keys[lo:lo + h], None if values is None else values[lo:lo + h],
+                           descending=descending, key_type=kt)
+        w.my_sort()
+        for r, lo, h in blocks:
+            w.store_columns(r, out_k[lo:lo + h], out_v[lo:lo + h], descending=descending, key_type=kt)
+    return out_k, out_v
 
 
 def get_unique_id() -> bytes:
@@ -413,6 +511,48 @@ class World:
         _check(_lib().lsb_copy_out(self._h, rank, off, cnt, out.ctypes.data if cnt else None),
                "lsb_copy_out")
         return out
+
+    def load_columns(self, rank: int, keys, values=None, off: int = 0, descending: bool = False,
+                     key_type: Optional[int] = None) -> None:
+        """lsb_load_columns: slots [off, off + len(keys)) of `rank` from device
+        columns (1-D contiguous CUDA torch tensors).  The keys' dtype gives the
+        key type (key_type= overrides it); values: any 4- or 8-byte dtype, or
+        None for the records' global indices (the sort is then an argsort).
+        torch's current stream is synchronized first; the call returns when
+        the records are in place."""
+        import torch
+        _check_column(keys, "keys")
+        kt = _key_type_of(keys, key_type)
+        vb, vp = 0, None
+        if values is not None:
+            _check_column(values, "values", keys.device)
+            if values.numel() != keys.numel():
+                raise ValueError("keys and values differ in length")
+            vb, vp = values.element_size(), values.data_ptr()
+        torch.cuda.current_stream(keys.device).synchronize()
+        _check(_lib().lsb_load_columns(self._h, rank, off, keys.numel(), keys.data_ptr(), kt, vp, vb,
+                                       ORDER_DESCENDING if descending else 0), "lsb_load_columns")
+
+    def store_columns(self, rank: int, keys=None, values=None, off: int = 0, descending: bool = False,
+                      key_type: Optional[int] = None) -> None:
+        """lsb_store_columns: slots [off, off + len) of `rank` into device
+        columns, with the key type and order the load was given.  keys or
+        values may be None (not both); 4-byte values get the low word."""
+        import torch
+        if keys is None and values is None:
+            raise ValueError("no output column")
+        cols = [t for t in (keys, values) if t is not None]
+        for t, what in ((keys, "keys"), (values, "values")):
+            if t is not None:
+                _check_column(t, what, cols[0].device)
+        if len(cols) == 2 and keys.numel() != values.numel():
+            raise ValueError("keys and values differ in length")
+        kt = _key_type_of(keys, key_type) if keys is not None else (KEY_U64 if key_type is None else key_type)
+        vb, vp = (values.element_size(), values.data_ptr()) if values is not None else (0, None)
+        torch.cuda.current_stream(cols[0].device).synchronize()
+        _check(_lib().lsb_store_columns(self._h, rank, off, cols[0].numel(),
+                                        None if keys is None else keys.data_ptr(), kt, vp, vb,
+                                        ORDER_DESCENDING if descending else 0), "lsb_store_columns")
 
     def scatter_global(self, arr: np.ndarray) -> None:
         """Load a global array of n records into the block partition."""

@@ -256,6 +256,75 @@ int  lsb_generate_ex(lsb_ctx_t* ctx, int dist, double param);
 int  lsb_copy_in(lsb_ctx_t* ctx, int rank, int64_t off, int64_t cnt, const lsb_elem_t* host);
 int  lsb_copy_out(lsb_ctx_t* ctx, int rank, int64_t off, int64_t cnt, lsb_elem_t* host);
 
+/* ---- caller-owned device columns ------------------------------------------ */
+/* A caller on the GPU (the reference's mySort stub, a torch pipeline) holds
+ * separate key and value arrays on the device.  lsb_load_columns turns them
+ * into the records of A, lsb_store_columns turns A back into columns; no byte
+ * passes through host memory.
+ * A key's raw bits are mapped to the unsigned 64-bit key the passes sort by:
+ *   LSB_KEY_U64               identity
+ *   LSB_KEY_I64               bit 63 flipped
+ *   LSB_KEY_F64               sign set: ~bits; else bit 63 flipped
+ *   LSB_KEY_U32 / I32 / F32   the same rules at 32 bits, zero-extended
+ * LSB_ORDER_DESCENDING (flags bit 0) complements that key within the key's
+ * width.  32-bit keys keep a zero upper word in both orders, so lsb_sort
+ * skips their four upper digits.  The sort is the stable ascending sort of
+ * the mapped key: equal keys keep their input order in both directions (the
+ * rule of a stable descending sort, e.g. torch.sort(stable=True,
+ * descending=True)).
+ * Float keys sort in the order of their bits, ascending:
+ *   1. NaNs with the sign bit set
+ *   2. -inf
+ *   3. finite values, -0.0 before +0.0
+ *   4. +inf
+ *   5. NaNs with the sign bit clear
+ * (descending: the reverse).  Keys come back bit for bit, NaN payloads and
+ * the sign of zero included. */
+#define LSB_KEY_U64 0
+#define LSB_KEY_I64 1
+#define LSB_KEY_F64 2
+#define LSB_KEY_U32 3
+#define LSB_KEY_I32 4
+#define LSB_KEY_F32 5
+#define LSB_ORDER_DESCENDING 1
+/* The mapping itself and its inverse: pure host functions, no device needed
+ * (the kernels run the same code).  A 32-bit type takes and returns its key
+ * in the low word.  0 on an unknown type or flag. */
+uint64_t lsb_key_encode(uint64_t bits, int key_type, int flags);
+uint64_t lsb_key_decode(uint64_t key, int key_type, int flags);
+/* Load: A[off + i] = {encode(keys_dev[i]), value} for i in [0, cnt), slots of
+ * local rank `rank` as for lsb_copy_in.  The value is vals_dev[i]: 8 bytes
+ * raw (val_bytes 8) or 4 bytes zero-extended (val_bytes 4); with vals_dev
+ * NULL and val_bytes 0 it is the record's global index rank * per + off + i,
+ * the reference's value (mpi/mpi_lsbsort.cpp:650-656), so the sorted values
+ * are the stable argsort.
+ * Store: the inverse, keys_dev[i] = decode(A[off + i].key) and vals_dev[i] =
+ * the value (val_bytes 8) or its low word (val_bytes 4).  Either output may
+ * be NULL (val_bytes 0 with vals_dev NULL), not both.
+ * Both calls are stateless: the caller gives the store the key_type and flags
+ * it gave the load; the context remembers neither.  They work alike in every
+ * kind of context.  cnt == 0 returns LSB_OK and launches nothing.
+ * Streams: the call waits for the rank's own stream, runs one kernel on it
+ * and returns once that kernel has finished.  It does not wait for any other
+ * stream: the caller's arrays must be ready (written, or free to overwrite)
+ * when the call is made.
+ * LSB_ERR_INVALID, before any kernel is launched: bad rank or range; unknown
+ * key type; unknown flag bits; val_bytes not 0, 4 or 8, or disagreeing with
+ * vals_dev; a pointer not aligned to its element size; a pointer that
+ * hipPointerGetAttributes does not report as device or managed memory of the
+ * rank's device (a pageable host pointer never reaches a kernel); a range
+ * [ptr, ptr + cnt * element size) that leaves the allocation
+ * hipMemGetAddressRange reports for ptr.  Columns aligned to 16 bytes are
+ * moved in 16-byte accesses, others element by element, with equal results.
+ * lsb_check_sorted works on loaded data (it compares the mapped keys);
+ * lsb_verify does not (PCG input only). */
+int  lsb_load_columns(lsb_ctx_t* ctx, int rank, int64_t off, int64_t cnt,
+                      const void* keys_dev, int key_type,
+                      const void* vals_dev, int val_bytes, int flags);
+int  lsb_store_columns(lsb_ctx_t* ctx, int rank, int64_t off, int64_t cnt,
+                       void* keys_dev, int key_type,
+                       void* vals_dev, int val_bytes, int flags);
+
 /* ---- the hot path ------------------------------------------------------- */
 /* == mySort(A, B): all 64/radix_bits passes; result in A.  Asynchronous
  * with respect to the host except for the per-pass count exchange when
@@ -307,7 +376,9 @@ int  lsb_barrier(lsb_ctx_t* ctx);
  * out[i].val < n, out[i].key == pcg64(val / per)[val % per] and
  * (key, val)[i] < (key, val)[i+1] strictly, across rank boundaries too.
  * Returns LSB_OK when all hold, LSB_ERR_VERIFY otherwise; *first_bad gets
- * the smallest failing global index (or -1). */
+ * the smallest failing global index (or -1).  PCG input only: records from
+ * lsb_copy_in or lsb_load_columns fail it (lsb_check_sorted is the check for
+ * those). */
 int  lsb_verify(lsb_ctx_t* ctx, int64_t* first_bad);
 /* == checkSorted (shmem/shmem_lsbsort.cpp:180-219): key order inside every
  * rank and across rank boundaries.  *sorted = 1 / 0. */

@@ -9,6 +9,10 @@
 //     the slice, chunk and whole-key waves tile every send and receive range
 //     once, and sender and receiver agree at every step;
 //   - every argument check that returns before a device call;
+//   - the key forms of caller-owned columns (lsb_key_encode / lsb_key_decode,
+//     csrc/lsb_keyform.h): round trip, order and zero upper words over every
+//     type and flag, specials included; lsb_load_columns / lsb_store_columns
+//     with a null context and bad arguments;
 //   - lsb_create / lsb_create_rank_ops with no usable device: the failure
 //     path tears down a half-built context (no leak, no double free).
 #include <algorithm>
@@ -18,6 +22,7 @@
 #include <vector>
 
 #include "lsb.h"
+#include "lsb_keyform.h"
 #include "lsb_xgeom.h"
 
 static int fails = 0;
@@ -283,6 +288,52 @@ static void wholekey_case(std::mt19937_64& rng, int64_t n, int P, int slices) {
     }
 }
 
+// The key forms: decode(encode(x)) == x, the exported functions equal the
+// inline ones the kernels call, 32-bit types keep a zero upper word, and a
+// larger encoded key means a later place in the type's own order (descending:
+// an earlier one) for the values below, which are listed in ascending order.
+static void keyform_case(std::mt19937_64& rng) {
+  const uint64_t f64_asc[] = {0xfff8000000000001ull, 0xfff0000000000000ull, 0xc000000000000000ull,
+                              0x8000000000000001ull, 0x8000000000000000ull, 0x0000000000000000ull,
+                              0x0000000000000001ull, 0x4000000000000000ull, 0x7ff0000000000000ull,
+                              0x7ff8000000000001ull};
+  const uint64_t f32_asc[] = {0xffc00001u, 0xff800000u, 0xc0000000u, 0x80000001u, 0x80000000u,
+                              0x00000000u, 0x00000001u, 0x40000000u, 0x7f800000u, 0x7fc00001u};
+  const uint64_t i64_asc[] = {0x8000000000000000ull, 0xffffffffffffffffull, 0, 1, 0x7fffffffffffffffull};
+  const uint64_t i32_asc[] = {0x80000000u, 0xffffffffu, 0, 1, 0x7fffffffu};
+  const uint64_t u64_asc[] = {0, 1, 0x8000000000000000ull, 0xffffffffffffffffull};
+  const uint64_t u32_asc[] = {0, 1, 0x80000000u, 0xffffffffu};
+  struct { int kt; const uint64_t* v; int n; } lists[] = {
+      {LSB_KEY_U64, u64_asc, 4}, {LSB_KEY_I64, i64_asc, 5}, {LSB_KEY_F64, f64_asc, 10},
+      {LSB_KEY_U32, u32_asc, 4}, {LSB_KEY_I32, i32_asc, 5}, {LSB_KEY_F32, f32_asc, 10}};
+  for (const auto& l : lists)
+    for (int flags : {0, LSB_ORDER_DESCENDING}) {
+      const uint64_t mask = l.kt >= LSB_KEY_U32 ? 0xffffffffull : ~0ull;
+      for (int i = 0; i < l.n; ++i) {
+        const uint64_t e = lsb_key_encode(l.v[i], l.kt, flags);
+        CHECK(lsb_key_decode(e, l.kt, flags) == l.v[i], "special round trip");
+        CHECK((e & ~mask) == 0, "upper word zero");
+        if (i > 0) {
+          const uint64_t p = lsb_key_encode(l.v[i - 1], l.kt, flags);
+          CHECK(flags ? e < p : e > p, "specials in order");
+        }
+      }
+      for (int i = 0; i < 10000; ++i) {
+        const uint64_t x = rng();
+        const uint64_t e = lsb_key_encode(x, l.kt, flags);
+        CHECK(e == lsb::encode(x, l.kt, flags), "exported encode = inline encode");
+        CHECK(lsb_key_decode(e, l.kt, flags) == (x & mask), "random round trip");
+        CHECK(lsb::decode(e, l.kt, flags) == (x & mask), "inline round trip");
+        CHECK((e & ~mask) == 0, "upper word zero");
+      }
+    }
+  for (int kt : {-1, 6, 1 << 30})
+    CHECK(lsb_key_encode(5, kt, 0) == 0 && lsb_key_decode(5, kt, 0) == 0, "unknown type gives 0");
+  for (int flags : {2, 3, -1})
+    CHECK(lsb_key_encode(5, LSB_KEY_U64, flags) == 0 && lsb_key_decode(5, LSB_KEY_I32, flags) == 0,
+          "unknown flag gives 0");
+}
+
 static int noop_ag(void*, const void*, void*, size_t) { return 0; }
 static int noop_a2a(void*, const void*, const size_t*, const size_t*, void*, const size_t*,
                     const size_t*) { return 0; }
@@ -318,6 +369,13 @@ int main() {
   CHECK(lsb_sort(nullptr) == LSB_ERR_INVALID, "null ctx");
   CHECK(lsb_set_option(nullptr, 0, 0) == LSB_ERR_INVALID, "null ctx option");
   for (int code = 0; code < 8; ++code) CHECK(lsb_strerror(code) != nullptr, "strerror");
+  keyform_case(rng);
+  uint64_t col[4] = {0, 1, 2, 3};  // host memory: never reaches a device call with a null context
+  CHECK(lsb_load_columns(nullptr, 0, 0, 4, col, LSB_KEY_U64, col, 8, 0) == LSB_ERR_INVALID, "load: null ctx");
+  CHECK(lsb_store_columns(nullptr, 0, 0, 4, col, LSB_KEY_U64, col, 8, 0) == LSB_ERR_INVALID, "store: null ctx");
+  CHECK(lsb_load_columns(nullptr, -1, -1, -1, nullptr, 6, nullptr, 3, 2) == LSB_ERR_INVALID, "load: all bad");
+  CHECK(lsb_store_columns(nullptr, 0, 0, 0, nullptr, LSB_KEY_F32, nullptr, 0, 0) == LSB_ERR_INVALID,
+        "store: null ctx, no column");
   CHECK(lsb_per_rank(10, 3) == 4 && lsb_here(10, 3, 2) == 2 && lsb_here(10, 3, 3) == 0, "geometry");
 
   // no usable device in this container: creation fails cleanly
