@@ -301,6 +301,7 @@ int lsb_generate_ex(lsb_ctx_t* c, int dist, double param) {
   } else {
     return fail(LSB_ERR_INVALID, "lsb_generate_ex", "dist");
   }
+  runs_invalidate(c);
   c->keygen = g;
   for (Rank& r : c->ranks) {
     HIP_TRY(hipSetDevice(r.dev));
@@ -320,6 +321,7 @@ int lsb_copy_in(lsb_ctx_t* c, int rank, int64_t off, int64_t cnt, const lsb_elem
   if (!r || off < 0 || cnt < 0 || off + cnt > c->per || (cnt > 0 && !host))
     return fail(LSB_ERR_INVALID, "lsb_copy_in", "rank or range");
   if (cnt == 0) return LSB_OK;
+  runs_invalidate(c);
   HIP_TRY(hipSetDevice(r->dev));
   HIP_TRY(hipStreamSynchronize(r->stream));
   HIP_TRY(hipMemcpy(r->A + off, host, (size_t)cnt * sizeof(Elem), hipMemcpyHostToDevice));
@@ -343,32 +345,6 @@ uint64_t lsb_key_encode(uint64_t bits, int key_type, int flags) { return lsb::en
 uint64_t lsb_key_decode(uint64_t key, int key_type, int flags) { return lsb::decode(key, key_type, flags); }
 
 namespace {
-
-// A caller's column of cnt elements of `elem` bytes at p, before a kernel may
-// touch it: aligned to its element, device (or managed) memory of the rank's
-// device as the runtime knows it, and [p, p + cnt * elem) inside the
-// allocation that holds p.  A pageable host pointer fails the second test.
-int check_column(const Rank& r, const void* p, size_t elem, int64_t cnt, const char* where) {
-  if (reinterpret_cast<uintptr_t>(p) % elem != 0) return fail(LSB_ERR_INVALID, where, "column not aligned to its element");
-  hipPointerAttribute_t at;
-  memset(&at, 0, sizeof at);
-  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(LSB_ERR_INVALID, where, "column is not device memory");
-  }
-  if ((at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged) || at.device != r.dev)
-    return fail(LSB_ERR_INVALID, where, "column is not device memory of the rank's device");
-  hipDeviceptr_t base = nullptr;
-  size_t size = 0;
-  if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(LSB_ERR_INVALID, where, "column's allocation unknown");
-  }
-  const uintptr_t lo = reinterpret_cast<uintptr_t>(base), at_p = reinterpret_cast<uintptr_t>(p);
-  if (at_p < lo || at_p - lo > size || (uint64_t)cnt > (size - (at_p - lo)) / elem)
-    return fail(LSB_ERR_INVALID, where, "column range leaves its allocation");
-  return LSB_OK;
-}
 
 // The checks lsb_load_columns and lsb_store_columns share; all of them come
 // before the first launch.  *rank_out: the rank, once every check has passed.
@@ -397,6 +373,7 @@ int lsb_load_columns(lsb_ctx_t* c, int rank, int64_t off, int64_t cnt, const voi
   LSB_TRY(check_columns(c, rank, off, cnt, keys_dev, key_type, vals_dev, val_bytes, flags, "lsb_load_columns", &r));
   if (cnt == 0) return LSB_OK;
   if (!keys_dev) return fail(LSB_ERR_INVALID, "lsb_load_columns", "null keys");
+  runs_invalidate(c);
   HIP_TRY(hipStreamSynchronize(r->stream));
   // The value of a record without one: its global index (mpi/mpi_lsbsort.cpp:650-656).
   const uint64_t val0 = (uint64_t)r->rank * (uint64_t)c->per + (uint64_t)off;
@@ -438,6 +415,7 @@ void quiesce(lsb_ctx* c) {
 int lsb_pass(lsb_ctx_t* c, int digit) {
   LSB_TRY(check_ctx(c));
   if (digit < 0 || digit >= 64 / c->bits) return fail(LSB_ERR_INVALID, "lsb_pass", "digit");
+  runs_invalidate(c);
   // Filed under the digit's own local passes (a 64-bit digit: the whole sort).
   c->pass_cursor = c->bits == 64 ? 0 : digit * (c->bits / lsb::kDigitBits);
   const int rc = do_pass(c, digit);
@@ -493,6 +471,7 @@ int lsb_sort(lsb_ctx_t* c) {
   LSB_TRY(check_ctx(c));
   if (c->broken)
     return fail(LSB_ERR_STATE, "lsb_sort", "an earlier sort failed and left packed records in A; load the input again");
+  runs_invalidate(c);
   const int rc = sort_body(c);
   if (rc != LSB_OK) quiesce(c);
   return rc;

@@ -172,6 +172,9 @@ void free_rank(Rank& r, const lsb_ctx* c) {
   (void)hipFree(r.split_fin_gather);
   (void)hipHostFree(r.split_h);
   (void)hipFree(r.merge_path);
+  (void)hipFree(r.run_cnt);
+  (void)hipFree(r.run_tbase);
+  (void)hipFree(r.run_sum);
   (void)hipFree(r.os_status);
   (void)hipFree(r.os_status2);
   (void)hipFree(r.rg_buf);
@@ -228,6 +231,32 @@ Rank* local_rank(lsb_ctx* c, int rank) {
   const int i = rank - c->first_rank;
   if (i < 0 || i >= (int)c->ranks.size()) return nullptr;
   return &c->ranks[i];
+}
+
+// A caller's column of cnt elements of `elem` bytes at p, before a kernel may
+// touch it: aligned to its element, device (or managed) memory of the rank's
+// device as the runtime knows it, and [p, p + cnt * elem) inside the
+// allocation that holds p.  A pageable host pointer fails the second test.
+int check_column(const Rank& r, const void* p, size_t elem, int64_t cnt, const char* where) {
+  if (reinterpret_cast<uintptr_t>(p) % elem != 0) return fail(LSB_ERR_INVALID, where, "column not aligned to its element");
+  hipPointerAttribute_t at;
+  memset(&at, 0, sizeof at);
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(LSB_ERR_INVALID, where, "column is not device memory");
+  }
+  if ((at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged) || at.device != r.dev)
+    return fail(LSB_ERR_INVALID, where, "column is not device memory of the rank's device");
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(LSB_ERR_INVALID, where, "column's allocation unknown");
+  }
+  const uintptr_t lo = reinterpret_cast<uintptr_t>(base), at_p = reinterpret_cast<uintptr_t>(p);
+  if (at_p < lo || at_p - lo > size || (uint64_t)cnt > (size - (at_p - lo)) / elem)
+    return fail(LSB_ERR_INVALID, where, "column range leaves its allocation");
+  return LSB_OK;
 }
 
 // ---- collectives of a one-rank-per-process context -------------------------

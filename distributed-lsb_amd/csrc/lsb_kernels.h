@@ -420,4 +420,31 @@ hipError_t launch_verify(const Elem* A, int64_t here, int64_t gbase, int64_t n, 
 // Key-only local sortedness (checkSorted); *unsorted set to 1 on a descent.
 hipError_t launch_check_sorted(const Elem* A, int64_t here, unsigned int* unsorted, hipStream_t s);
 
+// Runs of equal keys (lsb_runs.hip; lsb_count_runs / lsb_store_runs,
+// include/lsb.h).  A head is a position i in [1, here) with
+// A[i].key != A[i-1].key; position 0 is never counted (the host planner
+// decides it from the previous rank: head0).  The rank's records are tiles
+// of kTile, run_tiles(here) of them.
+inline int64_t run_tiles(int64_t here) { return (here + kTile - 1) / kTile; }
+constexpr int kRunSumWords = 5;  // sum[0..3]: first key, last key, inner, lead; sum[4]: error word
+// One read of A (here > 0): tile_cnt[t] = heads of tile t; tile_base[t] = heads
+// of the tiles before it; sum[0..3] = the rank's summary words (first and
+// last key, the number of heads, the smallest head or `here`).
+hipError_t launch_run_count(const Elem* A, int64_t here, uint32_t* tile_cnt, int64_t* tile_base, uint64_t* sum,
+                            hipStream_t s);
+// One more read of A.  With head j (in position order, position 0 among them
+// exactly when head0) at position i: keys[j] = decode(A[i].key), starts[j] =
+// gbase + i, firsts[j] = A[i].val (val_bytes 8) or its low word (4); then
+// counts[j] = starts[j + 1] - starts[j], the last one end - starts[j].  Any
+// output may be null (counts only with starts; firsts null exactly when
+// val_bytes is 0).  runs = head0 + the heads counted by launch_run_count:
+// every output holds that many elements.  A tile whose heads are not the
+// tile_cnt[t] of the count sets *err and writes nothing.
+// hipErrorInvalidValue on an unknown key type, flag or val_bytes, before any
+// launch.
+hipError_t launch_run_write(const Elem* A, int64_t here, int64_t gbase, int head0, const uint32_t* tile_cnt,
+                            const int64_t* tile_base, void* keys, int key_type, int flags, int64_t* starts,
+                            int64_t* counts, void* firsts, int val_bytes, int64_t runs, int64_t end,
+                            uint32_t* err, hipStream_t s);
+
 }  // namespace lsb

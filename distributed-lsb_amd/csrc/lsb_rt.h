@@ -10,6 +10,8 @@
 //                     gathered passes; loopback, RCCL / host ops, peer stores)
 //   lsb_wholekey.cpp  the whole-key exchange (splitter search, one all-to-all,
 //                     merge of the P runs)
+//   lsb_runs.cpp      runs of equal keys (lsb_plan_runs, lsb_count_runs,
+//                     lsb_store_runs)
 //   lsb_abi.cpp       the extern "C" entry points and the host planners
 //   lsb_xgeom.h       host-only exchange geometry (checked plan, waves); no
 //                     device header, so host tools can include it alone
@@ -150,6 +152,10 @@ struct Rank {
   int64_t* merge_path = nullptr;        // merge-path tile boundaries
   int split_q = 0, split_S = 0;         // geometry the split buffers were sized for
   std::vector<int64_t> mcut;            // [P][P * S + 1] cuts of every source (host)
+  // Runs of equal keys (lsb_runs.cpp), allocated on first use.
+  uint32_t* run_cnt = nullptr;          // [run_tiles(here)] heads per tile (k_run_count)
+  int64_t* run_tbase = nullptr;         // [run_tiles(here)] heads of the tiles before (k_run_scan)
+  uint64_t* run_sum = nullptr;          // [kRunSumWords] summary words, k_run_write's error word
   std::vector<int64_t> send_counts, send_displs, recv_counts, recv_displs;
 };
 
@@ -195,6 +201,12 @@ struct lsb_ctx {
   uint64_t last_varying = 0;
   int last_first = 0;  // the first pass's form (lsb_get_first_pass)
   int last_records = 0;  // the records between the passes (lsb_get_last_records)
+  // The plan of the last lsb_count_runs (lsb_plan_runs over every rank's
+  // summary), valid until an entry point that can change A (runs_invalidate).
+  bool runs_valid = false;
+  int64_t runs_total = 0;
+  std::vector<int> run_head0;                         // [P]
+  std::vector<int64_t> run_count, run_base, run_end;  // [P]
   lsb::KeyGen keygen;
   std::vector<lsb_rt::PendingEvent> pending;
   std::vector<std::pair<int, hipEvent_t>> event_pool;  // (device, event) of finished timings
@@ -341,6 +353,12 @@ void free_rank(Rank& r, const lsb_ctx* c = nullptr);
 int teardown_check(const lsb_ctx* c, const Rank& freeing);
 Rank* local_rank(lsb_ctx* c, int rank);
 int check_ctx(const lsb_ctx* c);
+// A is about to change: lsb_store_runs needs a new lsb_count_runs.
+inline void runs_invalidate(lsb_ctx* c) { c->runs_valid = false; }
+// A caller's column of cnt elements of `elem` bytes at p, before a kernel may
+// touch it (lsb_context.cpp): LSB_ERR_INVALID unless it is aligned to its element,
+// device (or managed) memory of the rank's device and inside its allocation.
+int check_column(const Rank& r, const void* p, size_t elem, int64_t cnt, const char* where);
 lsb_ctx* new_ctx(int64_t n_total, int num_ranks, int radix_bits);
 
 // ---- collectives (lsb_context.cpp) ------------------------------------------

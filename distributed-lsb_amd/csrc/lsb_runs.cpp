@@ -1,0 +1,193 @@
+// Runs of equal keys (include/lsb.h): the host planner over
+// the ranks' summary words, the collective count and the local store.
+#include "lsb_keyform.h"
+#include "lsb_rt.h"
+
+using namespace lsb_rt;
+
+namespace {
+
+// The planner's four words of rank s.
+enum { kFirst = 0, kLast = 1, kInner = 2, kLead = 3 };
+
+// Each buffer once: a call that failed part-way leaves what it got to the next.
+int ensure_run_scratch(Rank& r) {
+  const size_t tiles = (size_t)lsb::run_tiles(r.here);
+  if (!r.run_cnt) LSB_TRY(dev_alloc(&r.run_cnt, tiles));
+  if (!r.run_tbase) LSB_TRY(dev_alloc(&r.run_tbase, tiles));
+  if (!r.run_sum) LSB_TRY(dev_alloc(&r.run_sum, lsb::kRunSumWords));
+  return LSB_OK;
+}
+
+// Two outputs of cap elements (of ea and eb bytes) share a byte.
+bool columns_overlap(const void* a, size_t ea, const void* b, size_t eb, int64_t cap) {
+  if (!a || !b) return false;
+  const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+  return pa < pb + (uintptr_t)cap * eb && pb < pa + (uintptr_t)cap * ea;
+}
+
+// Every rank's four summary words on the host, the way gather_boundaries
+// moves its four: loopback reads each rank's own, a one-rank-per-process
+// context all-gathers them through r.gather.  Empty ranks give zeros.
+int gather_summaries(lsb_ctx* c, std::vector<uint64_t>& sum) {
+  const int P = c->P;
+  sum.assign((size_t)P * 4, 0);
+  if (c->mode == Mode::kLoopback) {
+    for (Rank& r : c->ranks) {
+      if (r.here == 0) continue;
+      HIP_TRY(hipSetDevice(r.dev));
+      HIP_TRY(hipStreamSynchronize(r.stream));
+      HIP_TRY(hipMemcpy(&sum[(size_t)r.rank * 4], r.run_sum, 32, hipMemcpyDeviceToHost));
+    }
+    return LSB_OK;
+  }
+  Rank& r = c->ranks[0];
+  HIP_TRY(hipSetDevice(r.dev));
+  uint64_t* d = r.gather;  // >= 4 * P entries
+  HIP_TRY(hipMemsetAsync(d, 0, sizeof(uint64_t) * 4 * P, r.stream));
+  if (r.here > 0)
+    HIP_TRY(hipMemcpyAsync(d + (size_t)r.rank * 4, r.run_sum, 32, hipMemcpyDeviceToDevice, r.stream));
+  LSB_TRY(coll_allgather_u64(c, r, d + (size_t)r.rank * 4, d, 4));
+  HIP_TRY(hipMemcpyAsync(sum.data(), d, sizeof(uint64_t) * 4 * P, hipMemcpyDeviceToHost, r.stream));
+  HIP_TRY(hipStreamSynchronize(r.stream));
+  return LSB_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lsb_plan_runs(int64_t n_total, int num_ranks, const uint64_t* summary, int* head0, int64_t* runs,
+                  int64_t* bases, int64_t* ends, int64_t* total) {
+  if (n_total < 0 || num_ranks < 1 || num_ranks > LSB_MAX_RANKS || !summary || !head0 || !runs || !bases || !ends ||
+      !total)
+    return fail(LSB_ERR_INVALID, "lsb_plan_runs", "arguments");
+  const int P = num_ranks;
+  const int64_t per = div_ceil(n_total, P);
+  // A summary no array gives is refused before anything is derived from it.
+  for (int r = 0; r < P; ++r) {
+    const int64_t here = here_of(n_total, P, r);
+    if (here == 0) continue;
+    const uint64_t* w = summary + (size_t)r * 4;
+    const uint64_t h = (uint64_t)here;
+    if (w[kLead] < 1 || w[kLead] > h) return fail(LSB_ERR_INVALID, "lsb_plan_runs", "lead outside [1, here]");
+    if (w[kInner] > h - 1) return fail(LSB_ERR_INVALID, "lsb_plan_runs", "more heads than positions");
+    if ((w[kInner] == 0) != (w[kLead] == h))
+      return fail(LSB_ERR_INVALID, "lsb_plan_runs", "heads and leading run disagree");
+    if (w[kInner] == 0 && w[kFirst] != w[kLast])
+      return fail(LSB_ERR_INVALID, "lsb_plan_runs", "one run with two keys");
+  }
+  int64_t acc = 0;
+  int prev = -1;  // the last non-empty rank before r
+  for (int r = 0; r < P; ++r) {
+    const int64_t here = here_of(n_total, P, r);
+    head0[r] = 0;
+    runs[r] = 0;
+    bases[r] = acc;
+    ends[r] = 0;
+    if (here == 0) {
+      bases[r] = 0;
+      continue;
+    }
+    const uint64_t* w = summary + (size_t)r * 4;
+    head0[r] = (prev < 0 || summary[(size_t)prev * 4 + kLast] != w[kFirst]) ? 1 : 0;
+    runs[r] = (int64_t)w[kInner] + head0[r];
+    acc += runs[r];
+    // The rank's last run goes on through the leading runs of the ranks
+    // after it for as long as they carry its key, whole ranks included.
+    int64_t end = (int64_t)r * per + here;
+    for (int s = r + 1; s < P; ++s) {
+      const int64_t hs = here_of(n_total, P, s);
+      if (hs == 0) continue;
+      const uint64_t* v = summary + (size_t)s * 4;
+      if (v[kFirst] != w[kLast]) break;
+      end += (int64_t)v[kLead];
+      if ((int64_t)v[kLead] < hs) break;
+    }
+    ends[r] = end;
+    prev = r;
+  }
+  *total = acc;
+  return LSB_OK;
+}
+
+int lsb_count_runs(lsb_ctx_t* c, int64_t* total, int64_t* runs, int64_t* bases) {
+  LSB_TRY(check_ctx(c));
+  if (!total) return fail(LSB_ERR_INVALID, "lsb_count_runs", "null total");
+  if (c->broken)
+    return fail(LSB_ERR_STATE, "lsb_count_runs", "an earlier sort failed and left packed records in A; load the input again");
+  runs_invalidate(c);
+  const int P = c->P;
+  std::vector<uint64_t> sum((size_t)P * 4, 0);
+  if (c->n > 0) {
+    for (Rank& r : c->ranks) {
+      if (r.here == 0) continue;
+      HIP_TRY(hipSetDevice(r.dev));
+      LSB_TRY(ensure_run_scratch(r));
+      HIP_TRY(lsb::launch_run_count(r.A, r.here, r.run_cnt, r.run_tbase, r.run_sum, r.stream));
+    }
+    LSB_TRY(gather_summaries(c, sum));
+  }
+  c->run_head0.assign(P, 0);
+  c->run_count.assign(P, 0);
+  c->run_base.assign(P, 0);
+  c->run_end.assign(P, 0);
+  c->runs_total = 0;
+  // The words come from the device (and from other ranks): the planner checks them.
+  if (lsb_plan_runs(c->n, P, sum.data(), c->run_head0.data(), c->run_count.data(), c->run_base.data(),
+                    c->run_end.data(), &c->runs_total) != LSB_OK)
+    return fail(LSB_ERR_STATE, "lsb_count_runs", "the device's run summary is inconsistent");
+  c->runs_valid = true;
+  *total = c->runs_total;
+  for (int r = 0; r < P; ++r) {
+    if (runs) runs[r] = c->run_count[r];
+    if (bases) bases[r] = c->run_base[r];
+  }
+  return LSB_OK;
+}
+
+int lsb_store_runs(lsb_ctx_t* c, int rank, int64_t cap, void* keys_dev, int key_type, int flags,
+                   int64_t* starts_dev, int64_t* counts_dev, void* firsts_dev, int val_bytes, int64_t* runs) {
+  const char* where = "lsb_store_runs";
+  LSB_TRY(check_ctx(c));
+  Rank* r = local_rank(c, rank);
+  if (!r || cap < 0) return fail(LSB_ERR_INVALID, where, "rank or cap");
+  if (!lsb::key_form_valid(key_type, flags)) return fail(LSB_ERR_INVALID, where, "key type or flags");
+  if (val_bytes != 0 && val_bytes != 4 && val_bytes != 8) return fail(LSB_ERR_INVALID, where, "val_bytes");
+  if ((val_bytes == 0) != (firsts_dev == nullptr)) return fail(LSB_ERR_INVALID, where, "val_bytes and firsts disagree");
+  if (!keys_dev && !starts_dev && !firsts_dev) return fail(LSB_ERR_INVALID, where, "no output");
+  if (counts_dev && !starts_dev) return fail(LSB_ERR_INVALID, where, "counts need starts");
+  if (!c->runs_valid) return fail(LSB_ERR_STATE, where, "no valid plan: call lsb_count_runs after the last change of A");
+  const int64_t mine = c->run_count[rank];
+  if (runs) *runs = mine;
+  if (cap < mine) return fail(LSB_ERR_INVALID, where, "cap below the rank's runs");
+  if (mine == 0) return LSB_OK;  // nothing to write: the pointers are not looked at
+  HIP_TRY(hipSetDevice(r->dev));
+  if (keys_dev) LSB_TRY(check_column(*r, keys_dev, (size_t)lsb::key_bytes(key_type), cap, where));
+  if (starts_dev) LSB_TRY(check_column(*r, starts_dev, 8, cap, where));
+  if (counts_dev) LSB_TRY(check_column(*r, counts_dev, 8, cap, where));
+  if (firsts_dev) LSB_TRY(check_column(*r, firsts_dev, (size_t)val_bytes, cap, where));
+  // Every range lies inside an allocation now, so the sums below cannot wrap.
+  const void* out[4] = {keys_dev, starts_dev, counts_dev, firsts_dev};
+  const size_t elem[4] = {(size_t)lsb::key_bytes(key_type), 8, 8, (size_t)val_bytes};
+  for (int i = 0; i < 4; ++i)
+    for (int j = i + 1; j < 4; ++j)
+      if (columns_overlap(out[i], elem[i], out[j], elem[j], cap))
+        return fail(LSB_ERR_INVALID, where, "outputs overlap");
+  HIP_TRY(hipStreamSynchronize(r->stream));
+  uint32_t* err = reinterpret_cast<uint32_t*>(r->run_sum + 4);
+  HIP_TRY(hipMemsetAsync(err, 0, sizeof(uint64_t), r->stream));
+  HIP_TRY(lsb::launch_run_write(r->A, r->here, (int64_t)r->rank * c->per, c->run_head0[rank], r->run_cnt,
+                                r->run_tbase, keys_dev, key_type, flags, starts_dev, counts_dev, firsts_dev,
+                                val_bytes, mine, c->run_end[rank], err, r->stream));
+  uint32_t h = 0;
+  HIP_TRY(hipMemcpyAsync(&h, err, sizeof h, hipMemcpyDeviceToHost, r->stream));
+  HIP_TRY(hipStreamSynchronize(r->stream));
+  if (h) {
+    runs_invalidate(c);
+    return fail(LSB_ERR_STATE, where, "A changed since lsb_count_runs: the outputs are unspecified");
+  }
+  return LSB_OK;
+}
+
+}  // extern "C"

@@ -19,10 +19,12 @@ seams so tests read like the reference program:
 
 A caller that holds keys and values on the GPU (1-D torch CUDA tensors; typed
 keys, either order, values or argsort) uses ``sort(keys, values)``, or
-``World.load_columns`` / ``World.store_columns`` around ``my_sort()``.  torch
-is imported only inside those functions.  A process that uses them imports
-torch before the first call into this module: the library then binds to the
-HIP runtime torch brought, and both see the same device memory.
+``World.load_columns`` / ``World.store_columns`` around ``my_sort()``; the
+groups of equal keys come from ``unique(keys)``, or ``World.count_runs`` /
+``World.store_runs`` after the sort.  torch is imported only inside those
+functions.  A process that uses them imports torch before the first call into
+this module: the library then binds to the HIP runtime torch brought, and both
+see the same device memory.
 
 Errors from the library raise :class:`LsbError` (the reference aborts on
 MPI errors, mpi/mpi_lsbsort.cpp:17-19).  There is no CPU fallback: if the
@@ -182,6 +184,9 @@ def _lib() -> ctypes.CDLL:
             "lsb_key_decode": (ctypes.c_uint64, [ctypes.c_uint64, i32, i32]),
             "lsb_load_columns": (i32, [vp, i32, i64, i64, vp, i32, vp, i32, i32]),
             "lsb_store_columns": (i32, [vp, i32, i64, i64, vp, i32, vp, i32, i32]),
+            "lsb_plan_runs": (i32, [i64, i32, vp, vp, vp, vp, vp, P64]),
+            "lsb_count_runs": (i32, [vp, P64, vp, vp]),
+            "lsb_store_runs": (i32, [vp, i32, i64, vp, i32, i32, vp, vp, vp, i32, P64]),
             "lsb_sort": (i32, [vp]),
             "lsb_pass": (i32, [vp, i32]),
             "lsb_sync": (i32, [vp]),
@@ -363,6 +368,65 @@ def sort(keys, values=None, descending: bool = False, ranks: int = 1, radix_bits
         for r, lo, h in blocks:
             w.store_columns(r, out_k[lo:lo + h], out_v[lo:lo + h], descending=descending, key_type=kt)
     return out_k, out_v
+
+
+def unique(keys, descending: bool = False, ranks: int = 1, radix_bits: int = 8,
+           key_type: Optional[int] = None):
+    """The distinct keys of a device column: (unique_keys, first_index, counts).
+
+    unique_keys: the distinct keys in sorted order (descending: reversed), in
+    the input's dtype; first_index: int64, the input index of each key's first
+    occurrence; counts: int64, how often it occurs.  Keys are equal when their
+    bits are: -0.0 and +0.0 are two keys, NaNs with different payloads too.
+    keys as for sort(); the input is left untouched, the outputs are fresh
+    tensors.  One World(n, ranks) loads the keys with index values, sorts,
+    counts the runs and stores each rank's into its part of the outputs."""
+    import torch
+    _check_column(keys, "keys")
+    kt = _key_type_of(keys, key_type)
+    if ranks < 1:
+        raise ValueError("ranks")
+    n = keys.numel()
+    if n == 0:
+        return (torch.empty_like(keys), torch.empty(0, dtype=torch.int64, device=keys.device),
+                torch.empty(0, dtype=torch.int64, device=keys.device))
+    dev = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
+    with World(n, ranks=ranks, devices=[dev] * ranks, radix_bits=radix_bits) as w:
+        for r in range(ranks):
+            lo, h = r * w.per, w.here(r)
+            if h:
+                w.load_columns(r, keys[lo:lo + h], None, descending=descending, key_type=kt)
+        w.my_sort()
+        plan = w.count_runs()
+        total = plan["total"]
+        out_k = torch.empty(total, dtype=keys.dtype, device=keys.device)
+        out_i = torch.empty(total, dtype=torch.int64, device=keys.device)
+        out_c = torch.empty(total, dtype=torch.int64, device=keys.device)
+        starts = torch.empty(total, dtype=torch.int64, device=keys.device)
+        for r in range(ranks):
+            lo, m = plan["bases"][r], plan["runs"][r]
+            if m:
+                w.store_runs(r, keys=out_k[lo:lo + m], starts=starts[lo:lo + m], counts=out_c[lo:lo + m],
+                             firsts=out_i[lo:lo + m], descending=descending, key_type=kt)
+    return out_k, out_i, out_c
+
+
+def plan_runs(n: int, P: int, summary: np.ndarray) -> dict:
+    """lsb_plan_runs, the host planner of the runs of equal keys: summary is
+    P x 4 uint64 (first key, last key, inner heads, leading run's length of
+    each rank) -> {"head0", "runs", "bases", "ends"} (P each) and "total"."""
+    summary = np.ascontiguousarray(summary, dtype=np.uint64)
+    if summary.shape != (P, 4):
+        raise ValueError("summary must be P x 4")
+    out = {k: np.zeros(P, dtype=np.int64) for k in ("runs", "bases", "ends")}
+    head0 = np.zeros(P, dtype=np.intc)
+    total = ctypes.c_int64()
+    _check(_lib().lsb_plan_runs(n, P, summary.ctypes.data, head0.ctypes.data, out["runs"].ctypes.data,
+                                out["bases"].ctypes.data, out["ends"].ctypes.data, ctypes.byref(total)),
+           "lsb_plan_runs")
+    out["head0"] = head0.astype(np.int64)
+    out["total"] = int(total.value)
+    return out
 
 
 def get_unique_id() -> bytes:
@@ -553,6 +617,52 @@ class World:
         _check(_lib().lsb_store_columns(self._h, rank, off, cols[0].numel(),
                                         None if keys is None else keys.data_ptr(), kt, vp, vb,
                                         ORDER_DESCENDING if descending else 0), "lsb_store_columns")
+
+    def count_runs(self) -> dict:
+        """lsb_count_runs: the runs of equal keys of the whole array (a
+        collective in a one-rank-per-process world).  {"total": runs of the
+        array, "runs": [P] runs each rank owns, "bases": [P] global index of
+        each rank's first run}; store_runs needs it, after the last change of
+        the records."""
+        total = ctypes.c_int64()
+        runs = np.zeros(self.P, dtype=np.int64)
+        bases = np.zeros(self.P, dtype=np.int64)
+        _check(_lib().lsb_count_runs(self._h, ctypes.byref(total), runs.ctypes.data, bases.ctypes.data),
+               "lsb_count_runs")
+        return {"total": int(total.value), "runs": [int(x) for x in runs], "bases": [int(x) for x in bases]}
+
+    def store_runs(self, rank: int, keys=None, starts=None, counts=None, firsts=None, descending: bool = False,
+                   key_type: Optional[int] = None) -> int:
+        """lsb_store_runs: the runs that start on `rank` into device columns
+        (1-D contiguous CUDA torch tensors, any of them None): keys with the
+        key type and order the load was given, starts and counts int64, firsts
+        any 4- or 8-byte dtype (4: the value's low word).  counts needs
+        starts.  Every column holds at least the rank's runs; -> that
+        number."""
+        import torch
+        cols = [(t, what) for t, what in ((keys, "keys"), (starts, "starts"), (counts, "counts"),
+                                          (firsts, "firsts")) if t is not None]
+        if not cols:
+            raise ValueError("no output column")
+        if counts is not None and starts is None:
+            raise ValueError("counts need starts")
+        for t, what in cols:
+            _check_column(t, what, cols[0][0].device)
+        for t, what in ((starts, "starts"), (counts, "counts")):
+            if t is not None and t.dtype != torch.int64:
+                raise ValueError(f"{what}: not int64")
+        cap = min(t.numel() for t, _ in cols)
+        kt = _key_type_of(keys, key_type) if keys is not None else (KEY_U64 if key_type is None else key_type)
+        if cap == 0:  # an empty tensor has no address: stand-ins say which outputs are meant (cap 0: never written)
+            keys, starts, counts, firsts = (None if t is None else t.new_empty(1)
+                                            for t in (keys, starts, counts, firsts))
+        vb, fp = (firsts.element_size(), firsts.data_ptr()) if firsts is not None else (0, None)
+        torch.cuda.current_stream(cols[0][0].device).synchronize()
+        runs = ctypes.c_int64()
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        _check(_lib().lsb_store_runs(self._h, rank, cap, ptr(keys), kt, ORDER_DESCENDING if descending else 0,
+                                     ptr(starts), ptr(counts), fp, vb, ctypes.byref(runs)), "lsb_store_runs")
+        return int(runs.value)
 
     def scatter_global(self, arr: np.ndarray) -> None:
         """Load a global array of n records into the block partition."""

@@ -325,6 +325,89 @@ int  lsb_store_columns(lsb_ctx_t* ctx, int rank, int64_t off, int64_t cnt,
                        void* keys_dev, int key_type,
                        void* vals_dev, int val_bytes, int flags);
 
+/* ---- runs of equal keys --------------------------------------------------- */
+/* What a caller does next with a sorted array: the distinct keys, how often
+ * each occurs, where each group starts and which input record was its first
+ * (dedup, histogram, group-by offsets, unique with index and counts), on the
+ * device and across rank boundaries.
+ * A run is a maximal range of adjacent global positions (rank 0's slots, then
+ * rank 1's, ...) whose records have the same mapped unsigned 64-bit key.  On a
+ * sorted array the runs are the groups of equal keys; the definition does not
+ * need sortedness (it is unique_consecutive on any array).
+ * Equality is equality of the key's bits: -0.0 and +0.0 are two keys, NaNs
+ * with different payloads are different keys, and every NaN equals itself.
+ * A run belongs to the rank that holds its first record; its count includes
+ * its records on later ranks.
+ *
+ * lsb_plan_runs: the host planner, pure host code.  summary[r][0..3] of a
+ * non-empty rank r (here(r) > 0; the words of empty ranks are ignored):
+ *   first  key of its first record        last   key of its last record
+ *   inner  number of i in [1, here) with key[i] != key[i-1]
+ *   lead   the smallest such i, or here when there is none
+ * Out, per rank (P entries each, zeros for empty ranks): head0[r] = 1 when a
+ * run starts at r's first slot; runs[r] = inner + head0, the runs r owns;
+ * bases[r] = the global index of r's first run (exclusive prefix sum of
+ * runs); ends[r] = the global position one past the end of the run that holds
+ * r's last record; *total = the number of runs.  LSB_ERR_INVALID on a null
+ * argument, n < 0, P outside [1, 64], or a summary no array gives: lead < 1,
+ * lead > here, inner > here - 1, (inner == 0) != (lead == here), or
+ * inner == 0 with first != last.
+ *
+ * lsb_count_runs: collective in one-rank-per-process contexts (every rank
+ * calls it, in the same order as its other collectives, as lsb_check_sorted).
+ * Reads every local rank's A once, gathers the ranks' summaries, runs the
+ * planner and keeps the plan in the context.  *total = the number of runs of
+ * the whole array; runs[P] and bases[P] (either may be NULL) as above, for
+ * every rank of the world.  n == 0: *total = 0, nothing is launched.  The
+ * first call allocates 12 bytes per 4096 records of scratch on each rank.
+ * The plan stays valid until lsb_generate, lsb_generate_ex, lsb_copy_in,
+ * lsb_load_columns, lsb_sort or lsb_pass is called.  In a one-rank-per-
+ * process world lsb_copy_in and lsb_load_columns are local calls and drop the
+ * plan of the calling process only, while the other ranks' plans depend on
+ * its records (a run's count reaches into later ranks): after any rank has
+ * changed its records, every rank calls lsb_count_runs again before its next
+ * lsb_store_runs.
+ * LSB_ERR_INVALID: null context or total.  LSB_ERR_STATE: an earlier sort
+ * left the context unusable (as lsb_sort), or the gathered summaries are not
+ * those of an array.
+ *
+ * lsb_store_runs: local, no collective; needs a valid plan (LSB_ERR_STATE
+ * otherwise).  Reads rank's A once more and writes, for the j-th run that
+ * starts on this rank, j in [0, runs[rank]):
+ *   keys_dev[j]   = decode(key) with key_type and flags as lsb_store_columns
+ *   starts_dev[j] = the global position of the run's first record
+ *   counts_dev[j] = the run's length (records on later ranks included)
+ *   firsts_dev[j] = the first record's value (val_bytes 8) or its low word
+ *                   (val_bytes 4); after a stable sort of a load without
+ *                   values this is the input index of the key's first
+ *                   occurrence
+ * Every output is optional and at least one is required; counts_dev needs
+ * starts_dev (the counts are the differences of the starts); firsts_dev NULL
+ * goes with val_bytes 0.  cap = the elements every given output holds.
+ * The outputs must not overlap one another.
+ * *runs (may be NULL) = runs[rank]; cap < runs[rank] returns LSB_ERR_INVALID
+ * with *runs set and nothing written.  A rank that owns no run returns LSB_OK
+ * and launches nothing; nothing would be written, so its output pointers are
+ * not examined (the pointer checks below do not apply to it).
+ * LSB_ERR_INVALID, before any kernel is launched: bad rank, cap < 0, unknown
+ * key type or flag bits, val_bytes not 0, 4 or 8 or disagreeing with
+ * firsts_dev, no output, counts_dev without starts_dev, and for each output
+ * the pointer checks of lsb_load_columns over cap elements (alignment, device
+ * memory of the rank's device, range inside its allocation), and two outputs
+ * whose ranges of cap elements share a byte.
+ * LSB_ERR_STATE after the kernel: A was changed behind the library's back
+ * since lsb_count_runs (a tile's heads differ from those counted); the
+ * outputs are then unspecified, nothing is written outside them, and the
+ * plan is dropped.
+ * Streams as lsb_store_columns: the call waits for the rank's stream, runs on
+ * it and returns when done. */
+int  lsb_plan_runs(int64_t n_total, int num_ranks, const uint64_t* summary,
+                   int* head0, int64_t* runs, int64_t* bases, int64_t* ends, int64_t* total);
+int  lsb_count_runs(lsb_ctx_t* ctx, int64_t* total, int64_t* runs, int64_t* bases);
+int  lsb_store_runs(lsb_ctx_t* ctx, int rank, int64_t cap, void* keys_dev, int key_type, int flags,
+                    int64_t* starts_dev, int64_t* counts_dev, void* firsts_dev, int val_bytes,
+                    int64_t* runs);
+
 /* ---- the hot path ------------------------------------------------------- */
 /* == mySort(A, B): all 64/radix_bits passes; result in A.  Asynchronous
  * with respect to the host except for the per-pass count exchange when

@@ -13,6 +13,10 @@
 //     csrc/lsb_keyform.h): round trip, order and zero upper words over every
 //     type and flag, specials included; lsb_load_columns / lsb_store_columns
 //     with a null context and bad arguments;
+//   - the planner of the runs of equal keys (lsb_plan_runs) against a count
+//     over the whole array: random, single-run, all-distinct and n < P
+//     arrays; corrupted summaries are refused; lsb_count_runs /
+//     lsb_store_runs with a null context and bad arguments;
 //   - lsb_create / lsb_create_rank_ops with no usable device: the failure
 //     path tears down a half-built context (no leak, no double free).
 #include <algorithm>
@@ -334,6 +338,100 @@ static void keyform_case(std::mt19937_64& rng) {
           "unknown flag gives 0");
 }
 
+// lsb_plan_runs on the block partition of a[0..n) over P ranks: the summary
+// words from their definition, the plan against a walk over the whole array.
+static void runs_case(const std::vector<uint64_t>& a, int P) {
+  const int64_t n = (int64_t)a.size(), per = lsb_per_rank(n, P);
+  std::vector<uint64_t> sum((size_t)P * 4, 0);
+  for (int r = 0; r < P; ++r) {
+    const int64_t here = lsb_here(n, P, r), lo = r * per;
+    if (here == 0) continue;
+    uint64_t inner = 0, lead = (uint64_t)here;
+    for (int64_t i = here - 1; i >= 1; --i)
+      if (a[(size_t)(lo + i)] != a[(size_t)(lo + i - 1)]) {
+        ++inner;
+        lead = (uint64_t)i;
+      }
+    sum[(size_t)r * 4 + 0] = a[(size_t)lo];
+    sum[(size_t)r * 4 + 1] = a[(size_t)(lo + here - 1)];
+    sum[(size_t)r * 4 + 2] = inner;
+    sum[(size_t)r * 4 + 3] = lead;
+  }
+  std::vector<int> head0(P, -7);
+  std::vector<int64_t> runs(P, -7), bases(P, -7), ends(P, -7);
+  int64_t total = -7;
+  CHECK(lsb_plan_runs(n, P, sum.data(), head0.data(), runs.data(), bases.data(), ends.data(), &total) == LSB_OK,
+        "plan_runs ok");
+  int64_t seen = 0;
+  for (int r = 0; r < P; ++r) {
+    const int64_t here = lsb_here(n, P, r), lo = r * per;
+    int64_t mine = 0;
+    for (int64_t i = lo; i < lo + here; ++i) mine += i == 0 || a[(size_t)i] != a[(size_t)(i - 1)];
+    int64_t end = lo + here;  // one past the run that holds the rank's last record
+    while (here > 0 && end < n && a[(size_t)end] == a[(size_t)(end - 1)]) ++end;
+    CHECK(runs[r] == mine, "runs = heads of the rank's positions");
+    CHECK(bases[r] == (here ? seen : 0), "bases are the prefix sums");
+    CHECK(ends[r] == (here ? end : 0), "ends");
+    CHECK(head0[r] == (here > 0 && (lo == 0 || a[(size_t)lo] != a[(size_t)(lo - 1)]) ? 1 : 0), "head0");
+    seen += mine;
+  }
+  CHECK(total == seen, "total");
+  // every corruption of a non-empty rank's words the header lists is refused
+  for (int r = 0; r < P; ++r) {
+    const uint64_t here = (uint64_t)lsb_here(n, P, r);
+    if (here == 0) continue;
+    const uint64_t* w = &sum[(size_t)r * 4];
+    const uint64_t bad[][4] = {{w[0], w[1], w[2], 0},          {w[0], w[1], w[2], here + 1},
+                               {w[0], w[1], w[2], ~0ull},      {w[0], w[1], here, w[3]},
+                               {w[0], w[1], ~0ull, w[3]},      {w[0], w[1], w[2] ? 0ull : 1ull, w[3]},
+                               {w[0], w[0] + 1, 0, here}};
+    for (const auto& b : bad) {
+      std::vector<uint64_t> s2(sum);
+      std::copy(b, b + 4, s2.begin() + (size_t)r * 4);
+      CHECK(lsb_plan_runs(n, P, s2.data(), head0.data(), runs.data(), bases.data(), ends.data(), &total) ==
+                LSB_ERR_INVALID, "corrupted summary refused");
+    }
+  }
+}
+
+static void runs_cases(std::mt19937_64& rng) {
+  for (int it = 0; it < 3000; ++it) {
+    const int64_t n = (int64_t)(rng() % 40);
+    const int P = 1 + (int)(rng() % 8), d = 1 + (int)(rng() % 5);
+    std::vector<uint64_t> a((size_t)n);
+    for (auto& x : a) x = rng() % d;
+    if (rng() % 2) std::sort(a.begin(), a.end());
+    runs_case(a, P);
+  }
+  for (int P : {1, 2, 3, 8, 64}) {
+    runs_case({}, P);
+    runs_case(std::vector<uint64_t>(37, 9), P);  // a single run
+    std::vector<uint64_t> d(41);
+    for (size_t i = 0; i < d.size(); ++i) d[i] = i * 3;
+    runs_case(d, P);                              // all distinct
+    runs_case({5, 5, 7}, P);                      // n < P for most P
+    runs_case({~0ull}, P);
+  }
+  std::vector<uint64_t> s(8, 0);
+  std::vector<int> h(2);
+  std::vector<int64_t> o(2);
+  int64_t t = 0;
+  CHECK(lsb_plan_runs(0, 2, nullptr, h.data(), o.data(), o.data(), o.data(), &t) == LSB_ERR_INVALID, "null summary");
+  CHECK(lsb_plan_runs(0, 2, s.data(), nullptr, o.data(), o.data(), o.data(), &t) == LSB_ERR_INVALID, "null head0");
+  CHECK(lsb_plan_runs(0, 2, s.data(), h.data(), o.data(), o.data(), o.data(), nullptr) == LSB_ERR_INVALID, "null total");
+  CHECK(lsb_plan_runs(-1, 2, s.data(), h.data(), o.data(), o.data(), o.data(), &t) == LSB_ERR_INVALID, "n < 0");
+  CHECK(lsb_plan_runs(0, 0, s.data(), h.data(), o.data(), o.data(), o.data(), &t) == LSB_ERR_INVALID, "P = 0");
+  CHECK(lsb_plan_runs(0, 65, s.data(), h.data(), o.data(), o.data(), o.data(), &t) == LSB_ERR_INVALID, "P = 65");
+  uint64_t col[4] = {0, 1, 2, 3};  // host memory: never reaches a device call with a null context
+  t = -5;
+  CHECK(lsb_count_runs(nullptr, &t, nullptr, nullptr) == LSB_ERR_INVALID && t == -5, "count_runs: null ctx");
+  CHECK(lsb_count_runs(nullptr, nullptr, o.data(), o.data()) == LSB_ERR_INVALID, "count_runs: all null");
+  CHECK(lsb_store_runs(nullptr, 0, 4, col, LSB_KEY_U64, 0, (int64_t*)col, (int64_t*)col, col, 8, &t) ==
+            LSB_ERR_INVALID && t == -5, "store_runs: null ctx");
+  CHECK(lsb_store_runs(nullptr, -1, -1, nullptr, 6, 2, nullptr, (int64_t*)col, nullptr, 3, nullptr) ==
+            LSB_ERR_INVALID, "store_runs: all bad");
+}
+
 static int noop_ag(void*, const void*, void*, size_t) { return 0; }
 static int noop_a2a(void*, const void*, const size_t*, const size_t*, void*, const size_t*,
                     const size_t*) { return 0; }
@@ -370,6 +468,7 @@ int main() {
   CHECK(lsb_set_option(nullptr, 0, 0) == LSB_ERR_INVALID, "null ctx option");
   for (int code = 0; code < 8; ++code) CHECK(lsb_strerror(code) != nullptr, "strerror");
   keyform_case(rng);
+  runs_cases(rng);
   uint64_t col[4] = {0, 1, 2, 3};  // host memory: never reaches a device call with a null context
   CHECK(lsb_load_columns(nullptr, 0, 0, 4, col, LSB_KEY_U64, col, 8, 0) == LSB_ERR_INVALID, "load: null ctx");
   CHECK(lsb_store_columns(nullptr, 0, 0, 4, col, LSB_KEY_U64, col, 8, 0) == LSB_ERR_INVALID, "store: null ctx");
