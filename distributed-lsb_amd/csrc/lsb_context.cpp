@@ -175,6 +175,8 @@ void free_rank(Rank& r, const lsb_ctx* c) {
   (void)hipFree(r.run_cnt);
   (void)hipFree(r.run_tbase);
   (void)hipFree(r.run_sum);
+  (void)hipFree(r.run_lead);
+  (void)hipFree(r.run_part);
   (void)hipFree(r.os_status);
   (void)hipFree(r.os_status2);
   (void)hipFree(r.rg_buf);

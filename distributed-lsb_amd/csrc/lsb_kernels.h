@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lsb_keyform.h"
+
 namespace lsb {
 
 // == SortElement (mpi/mpi_lsbsort.cpp:29-32); lsb_elem_t in the ABI.
@@ -446,5 +448,66 @@ hipError_t launch_run_write(const Elem* A, int64_t here, int64_t gbase, int head
                             const int64_t* tile_base, void* keys, int key_type, int flags, int64_t* starts,
                             int64_t* counts, void* firsts, int val_bytes, int64_t runs, int64_t end,
                             uint32_t* err, hipStream_t s);
+
+// Reductions over the values of a run (lsb_plan_reduce / lsb_store_reduce,
+// include/lsb.h).  (op, val_type) picks one of four
+// associative combines over 64-bit words: integer add, double add, and the
+// unsigned min / max of encode(value) (lsb_keyform.h's order of the type).
+// Values lie in memory as the caller's bits; red_load / red_store move them
+// into and out of the form the combine works on.  Host and device run the
+// same code: the planner folds the ranks' leads with what the kernels use.
+constexpr int kReduceSum = 0, kReduceMin = 1, kReduceMax = 2;  // == LSB_REDUCE_*
+enum RedForm { kRedAdd = 0, kRedFadd = 1, kRedMin = 2, kRedMax = 3 };
+inline bool reduce_valid(int op, int val_type) {
+  return op >= kReduceSum && op <= kReduceMax && val_type >= kKeyU64 && val_type <= kKeyF64;
+}
+inline int red_form(int op, int val_type) {
+  return op == kReduceSum ? (val_type == kKeyF64 ? kRedFadd : kRedAdd) : op == kReduceMin ? kRedMin : kRedMax;
+}
+template <int F>
+__host__ __device__ inline uint64_t red(uint64_t a, uint64_t b) {
+  if constexpr (F == kRedAdd) return a + b;
+  else if constexpr (F == kRedFadd)
+    return __builtin_bit_cast(uint64_t, __builtin_bit_cast(double, a) + __builtin_bit_cast(double, b));
+  else if constexpr (F == kRedMin) return a < b ? a : b;
+  else return a > b ? a : b;
+}
+__host__ __device__ inline uint64_t red(int form, uint64_t a, uint64_t b) {
+  switch (form) {
+    case kRedAdd: return red<kRedAdd>(a, b);
+    case kRedFadd: return red<kRedFadd>(a, b);
+    case kRedMin: return red<kRedMin>(a, b);
+    default: return red<kRedMax>(a, b);
+  }
+}
+// The combine's identity, in the working form: 0, -0.0 (x + -0.0 == x for
+// every double, -0.0 included), the largest and the smallest encoding.
+__host__ __device__ inline uint64_t red_identity(int form) {
+  return form == kRedFadd ? 0x8000000000000000ull : form == kRedMin ? ~0ull : 0ull;
+}
+__host__ __device__ inline bool red_encodes(int form) { return form == kRedMin || form == kRedMax; }
+__host__ __device__ inline uint64_t red_load(int form, uint64_t bits, const KeyForm& f) {
+  return red_encodes(form) ? encode(bits, f) : bits;
+}
+__host__ __device__ inline uint64_t red_store(int form, uint64_t x, const KeyForm& f) {
+  return red_encodes(form) ? decode(x, f) : x;
+}
+// The workgroup partials of launch_run_lead, at most (== kRunGridCap).
+constexpr int kRunLeadParts = 8192;
+// *out = op over A[0, lead).val (lead > 0): at most kRunLeadParts workgroup
+// partials into parts, then one workgroup over them.  The order and the
+// association of the combines depend on lead alone.
+hipError_t launch_run_lead(const Elem* A, int64_t lead, int op, int val_type, uint64_t* parts, uint64_t* out,
+                           hipStream_t s);
+// One more read of A after launch_run_count, then one workgroup.  out[j] = op
+// over the values of the records from head j up to the next head or the
+// rank's end, j as in launch_run_write (runs = head0 + the counted heads,
+// > 0); the rank's last run also takes `tail` (the caller's bits).
+// tile_lead[run_tiles(here)] is scratch: op over each tile's records in front
+// of its first head.  A tile whose heads are not the tile_cnt[t] of the count
+// sets *err and writes nothing; no index leaves [0, runs).
+hipError_t launch_run_reduce(const Elem* A, int64_t here, int head0, const uint32_t* tile_cnt,
+                             const int64_t* tile_base, int op, int val_type, uint64_t tail, uint64_t* tile_lead,
+                             uint64_t* out, int64_t runs, uint32_t* err, hipStream_t s);
 
 }  // namespace lsb

@@ -156,6 +156,8 @@ struct Rank {
   uint32_t* run_cnt = nullptr;          // [run_tiles(here)] heads per tile (k_run_count)
   int64_t* run_tbase = nullptr;         // [run_tiles(here)] heads of the tiles before (k_run_scan)
   uint64_t* run_sum = nullptr;          // [kRunSumWords] summary words, k_run_write's error word
+  uint64_t* run_lead = nullptr;         // [run_tiles(here)] k_run_reduce's tile leads (lsb_plan_reduce)
+  uint64_t* run_part = nullptr;         // [kRunLeadParts + 1] k_run_lead's partials, then the leading run's word
   std::vector<int64_t> send_counts, send_displs, recv_counts, recv_displs;
 };
 
@@ -207,6 +209,12 @@ struct lsb_ctx {
   int64_t runs_total = 0;
   std::vector<int> run_head0;                         // [P]
   std::vector<int64_t> run_count, run_base, run_end;  // [P]
+  std::vector<uint64_t> run_words;                    // [P][4] the gathered summary words
+  // The plan of the last lsb_plan_reduce (lsb_plan_run_tails over every
+  // rank's leading run); it dies with the run plan.
+  bool reduce_valid = false;
+  int reduce_op = 0, reduce_type = 0;
+  std::vector<uint64_t> run_tail;                     // [P]
   lsb::KeyGen keygen;
   std::vector<lsb_rt::PendingEvent> pending;
   std::vector<std::pair<int, hipEvent_t>> event_pool;  // (device, event) of finished timings
@@ -353,8 +361,9 @@ void free_rank(Rank& r, const lsb_ctx* c = nullptr);
 int teardown_check(const lsb_ctx* c, const Rank& freeing);
 Rank* local_rank(lsb_ctx* c, int rank);
 int check_ctx(const lsb_ctx* c);
-// A is about to change: lsb_store_runs needs a new lsb_count_runs.
-inline void runs_invalidate(lsb_ctx* c) { c->runs_valid = false; }
+// A is about to change: lsb_store_runs needs a new lsb_count_runs,
+// lsb_store_reduce a new lsb_plan_reduce after it.
+inline void runs_invalidate(lsb_ctx* c) { c->runs_valid = c->reduce_valid = false; }
 // A caller's column of cnt elements of `elem` bytes at p, before a kernel may
 // touch it (lsb_context.cpp): LSB_ERR_INVALID unless it is aligned to its element,
 // device (or managed) memory of the rank's device and inside its allocation.

@@ -1,5 +1,7 @@
 // Runs of equal keys (include/lsb.h): the host planner over
-// the ranks' summary words, the collective count and the local store.
+// the ranks' summary words, the collective count and the local store; and the
+// reductions over the runs' values (§7.3): the host planner over the ranks'
+// leading runs, the collective plan and the local store.
 #include "lsb_keyform.h"
 #include "lsb_rt.h"
 
@@ -10,12 +12,61 @@ namespace {
 // The planner's four words of rank s.
 enum { kFirst = 0, kLast = 1, kInner = 2, kLead = 3 };
 
+// A summary no array gives is refused before anything is derived from it
+// (lsb_plan_runs and lsb_plan_run_tails).
+int check_summary(int64_t n_total, int P, const uint64_t* summary, const char* where) {
+  for (int r = 0; r < P; ++r) {
+    const int64_t here = here_of(n_total, P, r);
+    if (here == 0) continue;
+    const uint64_t* w = summary + (size_t)r * 4;
+    const uint64_t h = (uint64_t)here;
+    if (w[kLead] < 1 || w[kLead] > h) return fail(LSB_ERR_INVALID, where, "lead outside [1, here]");
+    if (w[kInner] > h - 1) return fail(LSB_ERR_INVALID, where, "more heads than positions");
+    if ((w[kInner] == 0) != (w[kLead] == h)) return fail(LSB_ERR_INVALID, where, "heads and leading run disagree");
+    if (w[kInner] == 0 && w[kFirst] != w[kLast]) return fail(LSB_ERR_INVALID, where, "one run with two keys");
+  }
+  return LSB_OK;
+}
+
 // Each buffer once: a call that failed part-way leaves what it got to the next.
 int ensure_run_scratch(Rank& r) {
   const size_t tiles = (size_t)lsb::run_tiles(r.here);
   if (!r.run_cnt) LSB_TRY(dev_alloc(&r.run_cnt, tiles));
   if (!r.run_tbase) LSB_TRY(dev_alloc(&r.run_tbase, tiles));
   if (!r.run_sum) LSB_TRY(dev_alloc(&r.run_sum, lsb::kRunSumWords));
+  return LSB_OK;
+}
+
+// The reductions' scratch on top (lsb_plan_reduce), freed with the run scratch.
+int ensure_reduce_scratch(Rank& r) {
+  if (!r.run_lead) LSB_TRY(dev_alloc(&r.run_lead, (size_t)lsb::run_tiles(r.here)));
+  if (!r.run_part) LSB_TRY(dev_alloc(&r.run_part, (size_t)lsb::kRunLeadParts + 1));
+  return LSB_OK;
+}
+
+// Every rank's leading-run word on the host, the way gather_summaries moves
+// the summaries; ranks that reduced none (sent[r] == 0) give zeros.
+int gather_leads(lsb_ctx* c, const std::vector<char>& sent, std::vector<uint64_t>& lead) {
+  const int P = c->P;
+  lead.assign((size_t)P, 0);
+  if (c->mode == Mode::kLoopback) {
+    for (Rank& r : c->ranks) {
+      if (!sent[r.rank]) continue;
+      HIP_TRY(hipSetDevice(r.dev));
+      HIP_TRY(hipStreamSynchronize(r.stream));
+      HIP_TRY(hipMemcpy(&lead[(size_t)r.rank], r.run_part + lsb::kRunLeadParts, 8, hipMemcpyDeviceToHost));
+    }
+    return LSB_OK;
+  }
+  Rank& r = c->ranks[0];
+  HIP_TRY(hipSetDevice(r.dev));
+  uint64_t* d = r.gather;  // >= P entries
+  HIP_TRY(hipMemsetAsync(d, 0, sizeof(uint64_t) * P, r.stream));
+  if (sent[r.rank])
+    HIP_TRY(hipMemcpyAsync(d + r.rank, r.run_part + lsb::kRunLeadParts, 8, hipMemcpyDeviceToDevice, r.stream));
+  LSB_TRY(coll_allgather_u64(c, r, d + r.rank, d, 1));
+  HIP_TRY(hipMemcpyAsync(lead.data(), d, sizeof(uint64_t) * P, hipMemcpyDeviceToHost, r.stream));
+  HIP_TRY(hipStreamSynchronize(r.stream));
   return LSB_OK;
 }
 
@@ -64,19 +115,7 @@ int lsb_plan_runs(int64_t n_total, int num_ranks, const uint64_t* summary, int* 
     return fail(LSB_ERR_INVALID, "lsb_plan_runs", "arguments");
   const int P = num_ranks;
   const int64_t per = div_ceil(n_total, P);
-  // A summary no array gives is refused before anything is derived from it.
-  for (int r = 0; r < P; ++r) {
-    const int64_t here = here_of(n_total, P, r);
-    if (here == 0) continue;
-    const uint64_t* w = summary + (size_t)r * 4;
-    const uint64_t h = (uint64_t)here;
-    if (w[kLead] < 1 || w[kLead] > h) return fail(LSB_ERR_INVALID, "lsb_plan_runs", "lead outside [1, here]");
-    if (w[kInner] > h - 1) return fail(LSB_ERR_INVALID, "lsb_plan_runs", "more heads than positions");
-    if ((w[kInner] == 0) != (w[kLead] == h))
-      return fail(LSB_ERR_INVALID, "lsb_plan_runs", "heads and leading run disagree");
-    if (w[kInner] == 0 && w[kFirst] != w[kLast])
-      return fail(LSB_ERR_INVALID, "lsb_plan_runs", "one run with two keys");
-  }
+  LSB_TRY(check_summary(n_total, P, summary, "lsb_plan_runs"));
   int64_t acc = 0;
   int prev = -1;  // the last non-empty rank before r
   for (int r = 0; r < P; ++r) {
@@ -137,6 +176,7 @@ int lsb_count_runs(lsb_ctx_t* c, int64_t* total, int64_t* runs, int64_t* bases) 
   if (lsb_plan_runs(c->n, P, sum.data(), c->run_head0.data(), c->run_count.data(), c->run_base.data(),
                     c->run_end.data(), &c->runs_total) != LSB_OK)
     return fail(LSB_ERR_STATE, "lsb_count_runs", "the device's run summary is inconsistent");
+  c->run_words = sum;  // lsb_plan_reduce walks the same chains
   c->runs_valid = true;
   *total = c->runs_total;
   for (int r = 0; r < P; ++r) {
@@ -180,6 +220,98 @@ int lsb_store_runs(lsb_ctx_t* c, int rank, int64_t cap, void* keys_dev, int key_
   HIP_TRY(lsb::launch_run_write(r->A, r->here, (int64_t)r->rank * c->per, c->run_head0[rank], r->run_cnt,
                                 r->run_tbase, keys_dev, key_type, flags, starts_dev, counts_dev, firsts_dev,
                                 val_bytes, mine, c->run_end[rank], err, r->stream));
+  uint32_t h = 0;
+  HIP_TRY(hipMemcpyAsync(&h, err, sizeof h, hipMemcpyDeviceToHost, r->stream));
+  HIP_TRY(hipStreamSynchronize(r->stream));
+  if (h) {
+    runs_invalidate(c);
+    return fail(LSB_ERR_STATE, where, "A changed since lsb_count_runs: the outputs are unspecified");
+  }
+  return LSB_OK;
+}
+
+int lsb_plan_run_tails(int64_t n_total, int num_ranks, const uint64_t* summary, int op, int val_type,
+                       const uint64_t* lead, uint64_t* tail) {
+  const char* where = "lsb_plan_run_tails";
+  if (n_total < 0 || num_ranks < 1 || num_ranks > LSB_MAX_RANKS || !summary || !lead || !tail ||
+      !lsb::reduce_valid(op, val_type))
+    return fail(LSB_ERR_INVALID, where, "arguments");
+  const int P = num_ranks;
+  LSB_TRY(check_summary(n_total, P, summary, where));
+  const int F = lsb::red_form(op, val_type);
+  const lsb::KeyForm form = lsb::key_form(val_type, 0);
+  for (int r = 0; r < P; ++r) {
+    uint64_t acc = lsb::red_identity(F);
+    if (here_of(n_total, P, r) > 0) {
+      // lsb_plan_runs' walk for ends[r]: the leading runs of the ranks after r
+      // for as long as they carry its last key, whole ranks included.
+      const uint64_t* w = summary + (size_t)r * 4;
+      for (int s = r + 1; s < P; ++s) {
+        const int64_t hs = here_of(n_total, P, s);
+        if (hs == 0) continue;
+        const uint64_t* v = summary + (size_t)s * 4;
+        if (v[kFirst] != w[kLast]) break;
+        acc = lsb::red(F, acc, lsb::red_load(F, lead[s], form));
+        if ((int64_t)v[kLead] < hs) break;
+      }
+    }
+    tail[r] = lsb::red_store(F, acc, form);
+  }
+  return LSB_OK;
+}
+
+int lsb_plan_reduce(lsb_ctx_t* c, int op, int val_type) {
+  const char* where = "lsb_plan_reduce";
+  LSB_TRY(check_ctx(c));
+  if (!lsb::reduce_valid(op, val_type)) return fail(LSB_ERR_INVALID, where, "op or value type");
+  if (!c->runs_valid) return fail(LSB_ERR_STATE, where, "no valid plan: call lsb_count_runs after the last change of A");
+  c->reduce_valid = false;
+  const int P = c->P;
+  std::vector<uint64_t> lead((size_t)P, 0);
+  if (c->n > 0) {
+    // Ranks whose first slot goes on with an earlier rank's run reduce their leading run.
+    std::vector<char> sent((size_t)P, 0);
+    for (Rank& r : c->ranks) {
+      if (r.here == 0) continue;
+      HIP_TRY(hipSetDevice(r.dev));
+      LSB_TRY(ensure_reduce_scratch(r));
+      if (c->run_head0[r.rank]) continue;
+      HIP_TRY(lsb::launch_run_lead(r.A, (int64_t)c->run_words[(size_t)r.rank * 4 + kLead], op, val_type, r.run_part,
+                                   r.run_part + lsb::kRunLeadParts, r.stream));
+      sent[r.rank] = 1;
+    }
+    LSB_TRY(gather_leads(c, sent, lead));
+  }
+  c->run_tail.assign((size_t)P, 0);
+  if (lsb_plan_run_tails(c->n, P, c->run_words.data(), op, val_type, lead.data(), c->run_tail.data()) != LSB_OK)
+    return fail(LSB_ERR_STATE, where, "the run plan's summary is inconsistent");
+  c->reduce_op = op;
+  c->reduce_type = val_type;
+  c->reduce_valid = true;
+  return LSB_OK;
+}
+
+int lsb_store_reduce(lsb_ctx_t* c, int rank, int64_t cap, void* out_dev, int64_t* runs) {
+  const char* where = "lsb_store_reduce";
+  LSB_TRY(check_ctx(c));
+  Rank* r = local_rank(c, rank);
+  if (!r || cap < 0) return fail(LSB_ERR_INVALID, where, "rank or cap");
+  if (!c->runs_valid || !c->reduce_valid)
+    return fail(LSB_ERR_STATE, where, "no valid plan: call lsb_count_runs and lsb_plan_reduce after the last change of A");
+  const int64_t mine = c->run_count[rank];
+  if (runs) *runs = mine;
+  if (cap < mine) return fail(LSB_ERR_INVALID, where, "cap below the rank's runs");
+  if (mine == 0) return LSB_OK;  // nothing to write: the pointer is not looked at
+  if (!out_dev) return fail(LSB_ERR_INVALID, where, "null output");
+  HIP_TRY(hipSetDevice(r->dev));
+  LSB_TRY(check_column(*r, out_dev, 8, cap, where));
+  LSB_TRY(ensure_reduce_scratch(*r));
+  HIP_TRY(hipStreamSynchronize(r->stream));
+  uint32_t* err = reinterpret_cast<uint32_t*>(r->run_sum + 4);
+  HIP_TRY(hipMemsetAsync(err, 0, sizeof(uint64_t), r->stream));
+  HIP_TRY(lsb::launch_run_reduce(r->A, r->here, c->run_head0[rank], r->run_cnt, r->run_tbase, c->reduce_op,
+                                 c->reduce_type, c->run_tail[rank], r->run_lead, static_cast<uint64_t*>(out_dev), mine,
+                                 err, r->stream));
   uint32_t h = 0;
   HIP_TRY(hipMemcpyAsync(&h, err, sizeof h, hipMemcpyDeviceToHost, r->stream));
   HIP_TRY(hipStreamSynchronize(r->stream));

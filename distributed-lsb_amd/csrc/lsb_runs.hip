@@ -6,8 +6,18 @@
 //   k_run_write  one more read of A: every head writes its run's key, start
 //                and first value at its rank among the heads
 //   k_run_diff   counts from adjacent starts
+// and the reductions over the runs' values (lsb_plan_reduce /
+// lsb_store_reduce):
+//   k_run_reduce one more read of A: a segmented reduction per tile; a run's
+//                last record of the tile writes its value, the tile's leading
+//                part goes to tile_lead
+//   k_run_carry  one workgroup: the later tiles' leads and the later ranks'
+//                tail into the runs that go on past their tile
+//   k_run_lead, k_run_lead_sum  the values of a rank's leading run
 // No workgroup waits for another: a tile's base is ready before k_run_write
-// starts.  Positions, bases and counts are 64-bit throughout.
+// or k_run_reduce starts, every tile's lead before k_run_carry does.  No
+// floating-point atomics: the order of every addition is the code's.
+// Positions, bases and counts are 64-bit throughout.
 #include "lsb_kernels.h"
 #include "lsb_keyform.h"
 
@@ -226,6 +236,237 @@ __global__ __launch_bounds__(256) void k_run_diff(const int64_t* __restrict__ st
     counts[j] = (j + 1 < runs ? starts[j + 1] : end) - starts[j];
 }
 
+// ---- reductions over the values of a run --------------------
+static_assert(kRunLeadParts == kRunGridCap, "one partial per workgroup of k_run_lead");
+
+// x of another lane by DPP (every lane active): row_shr:k (0x110 + k) takes
+// the lane k below within a row of 16, row_bcast:15 (0x142) lane 15 of the row
+// before, row_bcast:31 (0x143) lane 31.  A lane without a source keeps its own
+// x; the scan does not use it there.
+template <int CTRL>
+__device__ __forceinline__ uint64_t dpp64(uint64_t x) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)x, (int)(uint32_t)x, CTRL, 0xf, 0xf, false);
+  const uint32_t hi =
+      (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)(x >> 32), (int)(uint32_t)(x >> 32), CTRL, 0xf, 0xf, false);
+  return ((uint64_t)hi << 32) | lo;
+}
+
+// The segmented inclusive reduction of v over the wave's lanes: lane l gets F
+// over the lanes [l - reach, l].  Rows of 16 first (a lane takes the lane k
+// below it while that lane is in its row and its segment), then lane 15 of
+// row 0 into row 1 and of row 2 into row 3, then lane 31 into the upper half,
+// each into the lanes whose segment reaches back that far.
+template <int F>
+__device__ __forceinline__ uint64_t wave_seg_scan(uint64_t v, int lane, int reach) {
+  const int in_row = lane & 15, in_half = lane & 31;
+  const int lim = reach < in_row ? reach : in_row;
+  uint64_t y = dpp64<0x111>(v);
+  if (1 <= lim) v = red<F>(y, v);
+  y = dpp64<0x112>(v);
+  if (2 <= lim) v = red<F>(y, v);
+  y = dpp64<0x114>(v);
+  if (4 <= lim) v = red<F>(y, v);
+  y = dpp64<0x118>(v);
+  if (8 <= lim) v = red<F>(y, v);
+  y = dpp64<0x142>(v);
+  if ((lane & 16) && in_row < reach) v = red<F>(y, v);
+  y = dpp64<0x143>(v);
+  if ((lane & 32) && in_half < reach) v = red<F>(y, v);
+  return v;
+}
+
+__device__ __forceinline__ uint64_t shfl_down64(uint64_t x, int off) {
+  return ((uint64_t)(uint32_t)__shfl_down((int)(uint32_t)(x >> 32), off, 64) << 32) |
+         (uint32_t)__shfl_down((int)(uint32_t)x, off, 64);
+}
+
+// out[h] = F over the values of the records from head h up to the next head
+// or the tile's end, h numbered as in k_run_write; tile_lead[t] = F over the
+// tile's records in front of its first head (the whole tile without one, the
+// identity when its first record is a head).  k_run_carry adds the later
+// tiles' leads to a run that goes on past its tile.
+// A segmented inclusive reduction in position order, keyed by the head
+// ballots: within an item across the lanes (wave_seg_scan, six DPP steps),
+// between a wave's items by the value of lane 63, between the four waves
+// through LDS.
+// The last record of a segment (the next position is a head, or the tile or
+// the rank ends there) holds the segment's value and writes it: every out[h]
+// and every tile_lead[t] is written once, by one lane.  The recount guards
+// all of it, as in k_run_write.
+template <int F>
+__global__ __launch_bounds__(kRunBlock) void k_run_reduce(const Elem* __restrict__ A, int64_t here, int64_t tiles,
+                                                          uint32_t head0, const uint32_t* __restrict__ tile_cnt,
+                                                          const int64_t* __restrict__ tile_base, int val_type,
+                                                          uint64_t* __restrict__ out,
+                                                          uint64_t* __restrict__ tile_lead,
+                                                          uint32_t* __restrict__ err) {
+  __shared__ uint32_t s_cell[kRunCells];
+  __shared__ uint32_t s_total;
+  __shared__ uint64_t s_part[kRunWaves];                   // a wave's records since its last head
+  __shared__ uint32_t s_has[kRunWaves], s_first[kRunWaves];  // a wave has a head; its first record is one
+  const int lane = run_lane(), wave = (int)(threadIdx.x >> 6);
+  const KeyForm form = key_form(val_type, 0);
+  const uint64_t le = ~0ull >> (63 - lane);  // the lanes at or below this one
+  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    uint64_t key[kRunItems], x[kRunItems], heads[kRunItems];
+    const int64_t wave0 = tile * kTile + (int64_t)wave * kRunWaveRecs;
+    wave_heads<true>(A, here, wave0, head0 != 0, key, x, heads);
+    uint64_t carry = red_identity(F), any = 0;
+#pragma unroll
+    for (int j = 0; j < kRunItems; ++j) {
+      uint64_t v = red_load(F, x[j], form);
+      const uint64_t m = heads[j] & le;
+      // the lanes below this one that belong to its segment
+      const int reach = m ? lane - (63 - __builtin_clzll(m)) : lane;
+      v = wave_seg_scan<F>(v, lane, reach);
+      if (m == 0) v = red<F>(carry, v);  // in front of the item's first head: the segment open at the item's start
+      carry = last_lane(v);
+      any |= heads[j];
+      x[j] = v;
+      if (lane == j) s_cell[wave * kRunItems + j] = (uint32_t)__popcll(heads[j]);
+    }
+    if (lane == 0) {
+      s_part[wave] = carry;
+      s_has[wave] = any != 0;
+      s_first[wave] = (uint32_t)(heads[0] & 1);
+    }
+    __syncthreads();
+    if (wave == 0) {  // cell counts -> exclusive prefixes, and their total
+      const uint32_t c = s_cell[lane];
+      uint32_t incl = c;
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t o = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += o;
+      }
+      s_cell[lane] = incl - c;
+      if (lane == 63) s_total = incl;
+    }
+    __syncthreads();
+    const uint32_t first = tile == 0 ? head0 : 0u;  // position 0 is the plan's, not the count's
+    if (s_total - first != tile_cnt[tile]) {
+      if (threadIdx.x == 0) atomicOr(err, 1u);
+    } else {
+      const int64_t out0 = tile_base[tile] + (int64_t)(head0 - first);
+      // What the waves before this one leave open at its first record.
+      uint64_t cw = red_identity(F);
+      for (int w = 0; w < wave; ++w) cw = s_has[w] ? s_part[w] : red<F>(cw, s_part[w]);
+      const uint64_t after = wave + 1 < kRunWaves ? s_first[wave + 1] : 1;  // the tile ends after wave 3
+      bool pre = true;  // no head of this wave in the items before j
+#pragma unroll
+      for (int j = 0; j < kRunItems; ++j) {
+        const int64_t i = wave0 + j * 64 + lane;
+        const uint64_t nb = j + 1 < kRunItems ? heads[(j + 1) % kRunItems] & 1 : after;
+        const uint64_t next = (heads[j] >> 1) | (nb << 63);  // the heads of the positions one up
+        const uint64_t m = heads[j] & le;
+        if (i < here && (((next >> lane) & 1) || i + 1 == here)) {
+          uint64_t v = x[j];
+          if (pre && m == 0) v = red<F>(cw, v);
+          v = red_store(F, v, form);
+          const uint32_t upto = s_cell[wave * kRunItems + j] + (uint32_t)__popcll(m);  // heads of the tile up to here
+          if (upto) out[out0 + upto - 1] = v;
+          else tile_lead[tile] = v;
+        }
+        pre = pre && heads[j] == 0;
+      }
+      if (threadIdx.x == 0 && (heads[0] & 1)) tile_lead[tile] = red_store(F, red_identity(F), form);
+    }
+    __syncthreads();
+  }
+}
+
+// One workgroup, chunked over adjacent tiles as k_run_scan.  A tile with a
+// head leaves its last run open; the leads of the tiles after it, up to and
+// including the next tile with a head (or the rank's last tile), belong to
+// that run and are folded into out at the tile's last head, in tile order;
+// the rank's last such run also takes `tail`.  Leads in front of the rank's
+// first head belong to an earlier rank's run and are dropped.  A thread folds
+// the runs that end inside its chunk itself; for its chunk's last one it walks
+// the later chunks' leading parts in LDS, so out[h] has one writer.
+__global__ __launch_bounds__(kRunScanBlock) void k_run_carry(int64_t tiles, uint32_t head0,
+                                                             const uint32_t* __restrict__ tile_cnt,
+                                                             const int64_t* __restrict__ tile_base,
+                                                             const uint64_t* __restrict__ tile_lead, int F,
+                                                             int val_type, uint64_t tail,
+                                                             uint64_t* __restrict__ out) {
+  __shared__ uint64_t s_pre[kRunScanBlock];  // a chunk's leads up to and including its first tile with a head
+  __shared__ uint32_t s_has[kRunScanBlock];  // the chunk has such a tile
+  const KeyForm form = key_form(val_type, 0);
+  const int t = (int)threadIdx.x;
+  const int64_t chunk = (tiles + kRunScanBlock - 1) / kRunScanBlock;
+  const int64_t lo = t * chunk < tiles ? t * chunk : tiles;
+  const int64_t hi = lo + chunk < tiles ? lo + chunk : tiles;
+  uint64_t acc = red_identity(F), pre = red_identity(F);
+  int64_t target = -1;  // the last head of the last tile with one, so far
+  for (int64_t i = lo; i < hi; ++i) {
+    acc = red(F, acc, red_load(F, tile_lead[i], form));
+    const uint32_t cnt = tile_cnt[i] + (i == 0 ? head0 : 0u);
+    if (cnt) {
+      if (target >= 0) out[target] = red_store(F, red(F, red_load(F, out[target], form), acc), form);
+      else pre = acc;
+      target = tile_base[i] + (i == 0 ? 0 : (int64_t)head0) + cnt - 1;
+      acc = red_identity(F);
+    }
+  }
+  s_pre[t] = target >= 0 ? pre : acc;
+  s_has[t] = target >= 0;
+  __syncthreads();
+  if (target >= 0) {
+    bool open = true;  // no later tile has a head: the run goes on to the rank's end
+    for (int k = t + 1; k < kRunScanBlock && open; ++k) {
+      acc = red(F, acc, s_pre[k]);
+      open = !s_has[k];
+    }
+    if (open) acc = red(F, acc, red_load(F, tail, form));
+    out[target] = red_store(F, red(F, red_load(F, out[target], form), acc), form);
+  }
+}
+
+// The workgroup's F over every thread's acc, in an order the code fixes (a
+// tree over each wave's lanes, then the waves in order); thread 0 has it.
+__device__ __forceinline__ uint64_t block_red(int F, uint64_t acc, uint64_t* s_wave) {
+  const int lane = run_lane();
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const uint64_t y = shfl_down64(acc, off);
+    if (lane + off < 64) acc = red(F, acc, y);
+  }
+  if (lane == 0) s_wave[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  for (int w = 1; w < kRunWaves; ++w) acc = red(F, acc, s_wave[w]);
+  return acc;
+}
+
+// parts[b] = F over the values of workgroup b's tiles of A[0, lead), tile by
+// tile in a grid stride.
+__global__ __launch_bounds__(kRunBlock) void k_run_lead(const Elem* __restrict__ A, int64_t lead, int F, int val_type,
+                                                        uint64_t* __restrict__ parts) {
+  __shared__ uint64_t s_wave[kRunWaves];
+  const KeyForm form = key_form(val_type, 0);
+  uint64_t acc = red_identity(F);
+  for (int64_t base = (int64_t)blockIdx.x * kTile; base < lead; base += (int64_t)gridDim.x * kTile)
+    for (int j = 0; j < kRunItems; ++j) {
+      const int64_t i = base + j * kRunBlock + threadIdx.x;
+      if (i < lead) acc = red(F, acc, red_load(F, A[i].val, form));
+    }
+  acc = block_red(F, acc, s_wave);
+  if (threadIdx.x == 0) parts[blockIdx.x] = red_store(F, acc, form);
+}
+
+// One workgroup: *out = F over parts[0, cnt), thread t taking cnt / kRunBlock
+// (rounded up) adjacent ones in index order.
+__global__ __launch_bounds__(kRunBlock) void k_run_lead_sum(const uint64_t* __restrict__ parts, int cnt, int F,
+                                                            int val_type, uint64_t* __restrict__ out) {
+  __shared__ uint64_t s_wave[kRunWaves];
+  const KeyForm form = key_form(val_type, 0);
+  const int chunk = (cnt + kRunBlock - 1) / kRunBlock;
+  uint64_t acc = red_identity(F);
+  for (int i = (int)threadIdx.x * chunk; i < ((int)threadIdx.x + 1) * chunk && i < cnt; ++i)
+    acc = red(F, acc, red_load(F, parts[i], form));
+  acc = block_red(F, acc, s_wave);
+  if (threadIdx.x == 0) *out = red_store(F, acc, form);
+}
+
 int run_grid(int64_t work, int block) {
   const int64_t g = (work + block - 1) / block;
   return (int)(g < 1 ? 1 : (g > kRunGridCap ? kRunGridCap : g));
@@ -259,6 +500,48 @@ hipError_t launch_run_write(const Elem* A, int64_t here, int64_t gbase, int head
                      (uint32_t)head0, tile_cnt, tile_base, keys, key_type, flags, starts, firsts, val_bytes, err);
   if (counts)
     hipLaunchKernelGGL(k_run_diff, dim3(run_grid(runs, 256)), dim3(256), 0, s, starts, counts, runs, end);
+  return hipGetLastError();
+}
+
+hipError_t launch_run_lead(const Elem* A, int64_t lead, int op, int val_type, uint64_t* parts, uint64_t* out,
+                           hipStream_t s) {
+  if (!reduce_valid(op, val_type) || lead <= 0 || !A || !parts || !out) return hipErrorInvalidValue;
+  const int F = red_form(op, val_type);
+  const int grid = run_grid(run_tiles(lead), 1);
+  hipLaunchKernelGGL(k_run_lead, dim3(grid), dim3(kRunBlock), 0, s, A, lead, F, val_type, parts);
+  hipLaunchKernelGGL(k_run_lead_sum, dim3(1), dim3(kRunBlock), 0, s, parts, grid, F, val_type, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_run_reduce(const Elem* A, int64_t here, int head0, const uint32_t* tile_cnt,
+                             const int64_t* tile_base, int op, int val_type, uint64_t tail, uint64_t* tile_lead,
+                             uint64_t* out, int64_t runs, uint32_t* err, hipStream_t s) {
+  if (!reduce_valid(op, val_type) || (head0 != 0 && head0 != 1) || here <= 0 || runs <= 0 || !A || !tile_cnt ||
+      !tile_base || !tile_lead || !out || !err)
+    return hipErrorInvalidValue;
+  const int64_t tiles = run_tiles(here);
+  const int F = red_form(op, val_type);
+  const dim3 grid(run_grid(tiles, 1)), block(kRunBlock);
+  switch (F) {
+    case kRedAdd:
+      hipLaunchKernelGGL(k_run_reduce<kRedAdd>, grid, block, 0, s, A, here, tiles, (uint32_t)head0, tile_cnt,
+                         tile_base, val_type, out, tile_lead, err);
+      break;
+    case kRedFadd:
+      hipLaunchKernelGGL(k_run_reduce<kRedFadd>, grid, block, 0, s, A, here, tiles, (uint32_t)head0, tile_cnt,
+                         tile_base, val_type, out, tile_lead, err);
+      break;
+    case kRedMin:
+      hipLaunchKernelGGL(k_run_reduce<kRedMin>, grid, block, 0, s, A, here, tiles, (uint32_t)head0, tile_cnt,
+                         tile_base, val_type, out, tile_lead, err);
+      break;
+    default:
+      hipLaunchKernelGGL(k_run_reduce<kRedMax>, grid, block, 0, s, A, here, tiles, (uint32_t)head0, tile_cnt,
+                         tile_base, val_type, out, tile_lead, err);
+      break;
+  }
+  hipLaunchKernelGGL(k_run_carry, dim3(1), dim3(kRunScanBlock), 0, s, tiles, (uint32_t)head0, tile_cnt, tile_base,
+                     tile_lead, F, val_type, tail, out);
   return hipGetLastError();
 }
 

@@ -21,7 +21,9 @@ A caller that holds keys and values on the GPU (1-D torch CUDA tensors; typed
 keys, either order, values or argsort) uses ``sort(keys, values)``, or
 ``World.load_columns`` / ``World.store_columns`` around ``my_sort()``; the
 groups of equal keys come from ``unique(keys)``, or ``World.count_runs`` /
-``World.store_runs`` after the sort.  torch is imported only inside those
+``World.store_runs`` after the sort, and one number per group from the value
+column (sum, min, max) from ``group_reduce(keys, values)``, or
+``World.plan_reduce`` / ``World.store_reduce``.  torch is imported only inside those
 functions.  A process that uses them imports torch before the first call into
 this module: the library then binds to the HIP runtime torch brought, and both
 see the same device memory.
@@ -72,6 +74,8 @@ MAX_PASSES = 16
 # Key forms of caller-owned columns (LSB_KEY_*, LSB_ORDER_DESCENDING).
 KEY_U64, KEY_I64, KEY_F64, KEY_U32, KEY_I32, KEY_F32 = range(6)
 ORDER_DESCENDING = 1
+# Reductions over the runs' values (LSB_REDUCE_*).
+REDUCE_SUM, REDUCE_MIN, REDUCE_MAX = range(3)
 
 
 class LsbError(RuntimeError):
@@ -187,6 +191,9 @@ def _lib() -> ctypes.CDLL:
             "lsb_plan_runs": (i32, [i64, i32, vp, vp, vp, vp, vp, P64]),
             "lsb_count_runs": (i32, [vp, P64, vp, vp]),
             "lsb_store_runs": (i32, [vp, i32, i64, vp, i32, i32, vp, vp, vp, i32, P64]),
+            "lsb_plan_run_tails": (i32, [i64, i32, vp, i32, i32, vp, vp]),
+            "lsb_plan_reduce": (i32, [vp, i32, i32]),
+            "lsb_store_reduce": (i32, [vp, i32, i64, vp, P64]),
             "lsb_sort": (i32, [vp]),
             "lsb_pass": (i32, [vp, i32]),
             "lsb_sync": (i32, [vp]),
@@ -411,6 +418,66 @@ def unique(keys, descending: bool = False, ranks: int = 1, radix_bits: int = 8,
     return out_k, out_i, out_c
 
 
+def _value_type_of(t) -> int:
+    """The LSB_KEY_* a value column's 64 bits are reduced as."""
+    import torch
+    table = {torch.int64: KEY_I64, torch.float64: KEY_F64}
+    if hasattr(torch, "uint64"):
+        table[torch.uint64] = KEY_U64
+    if t.dtype not in table:
+        raise ValueError(f"no reduction over {t.dtype} values (int64, float64, uint64)")
+    return table[t.dtype]
+
+
+def group_reduce(keys, values, op: str = "sum", descending: bool = False, ranks: int = 1, radix_bits: int = 8,
+                 key_type: Optional[int] = None):
+    """Group-by with one reduction: (unique_keys, reduced).
+
+    unique_keys: the distinct keys in sorted order (descending: reversed), in
+    the keys' dtype, as unique(); reduced[j]: op ("sum", "min", "max") over the
+    values of every record whose key is unique_keys[j], in the values' dtype
+    (int64, float64, or uint64 where torch has it).  Integer sums wrap; a
+    float64 sum is reproducible for given inputs and ranks; min and max follow
+    lsb.h's float order.  keys as for sort(); values the same length.  The
+    inputs are left untouched, the outputs are fresh tensors.  One
+    World(n, ranks) loads the columns, sorts, counts the runs, plans the
+    reduction and stores each rank's keys and values into its part of the
+    outputs."""
+    import torch
+    _check_column(keys, "keys")
+    kt = _key_type_of(keys, key_type)
+    _check_column(values, "values", keys.device)
+    vt = _value_type_of(values)
+    if values.numel() != keys.numel():
+        raise ValueError("keys and values differ in length")
+    ops = {"sum": REDUCE_SUM, "min": REDUCE_MIN, "max": REDUCE_MAX}
+    if op not in ops:
+        raise ValueError(f"op {op!r}: not one of {sorted(ops)}")
+    if ranks < 1:
+        raise ValueError("ranks")
+    n = keys.numel()
+    if n == 0:
+        return torch.empty_like(keys), torch.empty_like(values)
+    dev = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
+    with World(n, ranks=ranks, devices=[dev] * ranks, radix_bits=radix_bits) as w:
+        for r in range(ranks):
+            lo, h = r * w.per, w.here(r)
+            if h:
+                w.load_columns(r, keys[lo:lo + h], values[lo:lo + h], descending=descending, key_type=kt)
+        w.my_sort()
+        plan = w.count_runs()
+        w.plan_reduce(ops[op], vt)
+        total = plan["total"]
+        out_k = torch.empty(total, dtype=keys.dtype, device=keys.device)
+        out_v = torch.empty(total, dtype=values.dtype, device=keys.device)
+        for r in range(ranks):
+            lo, m = plan["bases"][r], plan["runs"][r]
+            if m:
+                w.store_runs(r, keys=out_k[lo:lo + m], descending=descending, key_type=kt)
+                w.store_reduce(r, out_v[lo:lo + m])
+    return out_k, out_v
+
+
 def plan_runs(n: int, P: int, summary: np.ndarray) -> dict:
     """lsb_plan_runs, the host planner of the runs of equal keys: summary is
     P x 4 uint64 (first key, last key, inner heads, leading run's length of
@@ -427,6 +494,21 @@ def plan_runs(n: int, P: int, summary: np.ndarray) -> dict:
     out["head0"] = head0.astype(np.int64)
     out["total"] = int(total.value)
     return out
+
+
+def plan_run_tails(n: int, P: int, summary: np.ndarray, op: int, val_type: int, lead: np.ndarray) -> np.ndarray:
+    """lsb_plan_run_tails, the host planner of the reductions over the runs'
+    values: summary as for plan_runs, lead[s] = op over the values of rank
+    s's leading run (uint64 bits) -> tail[P] (uint64 bits), what the ranks
+    after r add to r's last run."""
+    summary = np.ascontiguousarray(summary, dtype=np.uint64)
+    lead = np.ascontiguousarray(lead, dtype=np.uint64)
+    if summary.shape != (P, 4) or lead.shape != (P,):
+        raise ValueError("summary must be P x 4, lead P")
+    tail = np.zeros(P, dtype=np.uint64)
+    _check(_lib().lsb_plan_run_tails(n, P, summary.ctypes.data, op, val_type, lead.ctypes.data, tail.ctypes.data),
+           "lsb_plan_run_tails")
+    return tail
 
 
 def get_unique_id() -> bytes:
@@ -662,6 +744,30 @@ class World:
         ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
         _check(_lib().lsb_store_runs(self._h, rank, cap, ptr(keys), kt, ORDER_DESCENDING if descending else 0,
                                      ptr(starts), ptr(counts), fp, vb, ctypes.byref(runs)), "lsb_store_runs")
+        return int(runs.value)
+
+    def plan_reduce(self, op: int, val_type: int) -> None:
+        """lsb_plan_reduce: after count_runs, what the later ranks add to each
+        rank's last run under op (REDUCE_SUM, REDUCE_MIN, REDUCE_MAX) over the
+        records' values read as val_type (KEY_U64, KEY_I64, KEY_F64); a
+        collective in a one-rank-per-process world.  store_reduce needs it."""
+        _check(_lib().lsb_plan_reduce(self._h, op, val_type), "lsb_plan_reduce")
+
+    def store_reduce(self, rank: int, out) -> int:
+        """lsb_store_reduce: out[j] = the planned reduction over the values of
+        the j-th run that starts on `rank`, the indices of store_runs.  out: a
+        1-D contiguous CUDA torch tensor of 8-byte elements that holds at
+        least the rank's runs; -> that number."""
+        import torch
+        _check_column(out, "out")
+        if out.element_size() != 8:
+            raise ValueError("out: not 8-byte elements")
+        cap = out.numel()
+        if cap == 0:  # an empty tensor has no address (cap 0: never written)
+            out = out.new_empty(1)
+        torch.cuda.current_stream(out.device).synchronize()
+        runs = ctypes.c_int64()
+        _check(_lib().lsb_store_reduce(self._h, rank, cap, out.data_ptr(), ctypes.byref(runs)), "lsb_store_reduce")
         return int(runs.value)
 
     def scatter_global(self, arr: np.ndarray) -> None:

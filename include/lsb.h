@@ -408,6 +408,69 @@ int  lsb_store_runs(lsb_ctx_t* ctx, int rank, int64_t cap, void* keys_dev, int k
                     int64_t* starts_dev, int64_t* counts_dev, void* firsts_dev, int val_bytes,
                     int64_t* runs);
 
+/* Reductions over the runs' values: the group-by's last step, one number per
+ * run from the records' 64 value bits, across rank boundaries (a run's
+ * records on later ranks, whole middle ranks included, are part of it).
+ * op: LSB_REDUCE_SUM, LSB_REDUCE_MIN or LSB_REDUCE_MAX.  val_type names how
+ * the 64 value bits are read: LSB_KEY_U64, LSB_KEY_I64 or LSB_KEY_F64; the
+ * 32-bit types are refused (a value loaded with val_bytes 4 is zero-extended:
+ * reduce it as LSB_KEY_U64).
+ *   SUM  U64 and I64 add modulo 2^64 (the same bits).  F64 adds doubles: for
+ *        given (n, P, records) the result is bit-identical from call to call
+ *        (the code fixes the order and the association of the additions; no
+ *        atomics, no timing); it may differ between values of P.  The
+ *        identity combined with is -0.0 (0x8000000000000000), the additive
+ *        identity of IEEE doubles: a run of -0.0 values sums to -0.0.
+ *   MIN / MAX  in the order lsb_key_encode defines for the type, the float
+ *        order above included: -0.0 is below +0.0, a NaN with the sign clear
+ *        is the maximum of its run, one with the sign set its minimum.  The
+ *        result is one of the run's values, bit for bit.
+ * The identity of (op, val_type): SUM 0 (U64, I64) or -0.0 (F64); MIN the
+ * value whose encoding is all ones; MAX the value whose encoding is 0.
+ *
+ * lsb_plan_run_tails: the host planner, pure host code.  summary as for
+ * lsb_plan_runs (and checked the same way); lead[s] = op over the values of
+ * rank s's leading run, its first summary[s][lead] records (ignored for
+ * empty ranks and for ranks whose first slot starts a run).  tail[r] = op, in
+ * rank order, over lead[s] of the ranks after r whose leading run continues
+ * r's last run (the chain lsb_plan_runs walks for ends[r]); the identity when
+ * there is none, and for empty ranks.  LSB_ERR_INVALID on a null argument,
+ * n < 0, P outside [1, 64], an unknown op, a value type outside {U64, I64,
+ * F64}, or a summary lsb_plan_runs refuses.
+ *
+ * lsb_plan_reduce: collective in one-rank-per-process contexts, like
+ * lsb_count_runs; needs a valid run plan (LSB_ERR_STATE otherwise).  Every
+ * non-empty local rank whose first slot does not start a run reduces its
+ * leading run on its own stream; the words are gathered (8 bytes per rank),
+ * lsb_plan_run_tails runs on them, and the tails, op and val_type are kept in
+ * the context.  An unknown op or type returns LSB_ERR_INVALID before anything
+ * is launched or gathered.  n == 0 returns LSB_OK and launches nothing.  The
+ * reduce plan dies with the run plan; a later lsb_plan_reduce replaces it.
+ * The first call allocates, on each rank, 8 bytes per 4096 records and 64 KiB
+ * of scratch (freed with the context; lsb_rank_footprint models neither this
+ * nor lsb_count_runs' scratch).
+ *
+ * lsb_store_reduce: local, no collective; needs a reduce plan (LSB_ERR_STATE
+ * otherwise).  Reads rank's A once more and writes out_dev[j] = op over the
+ * values of all records of the j-th run that starts on this rank, j in
+ * [0, runs[rank]): the indices of lsb_store_runs.  out_dev is a column of cap
+ * 8-byte elements.  *runs (may be NULL) = runs[rank]; cap < runs[rank]
+ * returns LSB_ERR_INVALID with *runs set and nothing written.  A rank that
+ * owns no run returns LSB_OK, launches nothing and does not examine out_dev.
+ * LSB_ERR_INVALID, before any kernel is launched: bad rank, cap < 0, null
+ * out_dev, and the pointer checks of lsb_load_columns over cap 8-byte
+ * elements.  LSB_ERR_STATE after the kernel: A was changed behind the
+ * library's back since lsb_count_runs; the outputs are then unspecified,
+ * nothing is written outside [0, runs[rank]) and both plans are dropped.
+ * Streams as lsb_store_runs. */
+#define LSB_REDUCE_SUM 0
+#define LSB_REDUCE_MIN 1
+#define LSB_REDUCE_MAX 2
+int  lsb_plan_run_tails(int64_t n_total, int num_ranks, const uint64_t* summary,
+                        int op, int val_type, const uint64_t* lead, uint64_t* tail);
+int  lsb_plan_reduce(lsb_ctx_t* ctx, int op, int val_type);
+int  lsb_store_reduce(lsb_ctx_t* ctx, int rank, int64_t cap, void* out_dev, int64_t* runs);
+
 /* ---- the hot path ------------------------------------------------------- */
 /* == mySort(A, B): all 64/radix_bits passes; result in A.  Asynchronous
  * with respect to the host except for the per-pass count exchange when

@@ -17,6 +17,10 @@
 //     over the whole array: random, single-run, all-distinct and n < P
 //     arrays; corrupted summaries are refused; lsb_count_runs /
 //     lsb_store_runs with a null context and bad arguments;
+//   - the planner of the reductions over the runs' values
+//     (lsb_plan_run_tails) on the same partitions against a walk over the
+//     whole array; its refusals and identities; lsb_plan_reduce /
+//     lsb_store_reduce with a null context;
 //   - lsb_create / lsb_create_rank_ops with no usable device: the failure
 //     path tears down a half-built context (no leak, no double free).
 #include <algorithm>
@@ -338,6 +342,47 @@ static void keyform_case(std::mt19937_64& rng) {
           "unknown flag gives 0");
 }
 
+// lsb_plan_run_tails on the same partition, with the value of position i a
+// hash of i: lead[s] from its definition (garbage where the planner must not
+// look), tail[r] against a walk over the whole array from r's end on.  Wrapping
+// sums, and the min and max of the signed order: exact in any association.
+static uint64_t value_at(int64_t i) {
+  uint64_t z = ((uint64_t)i + 1) * 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+static uint64_t fold_values(int op, int val_type, int64_t lo, int64_t hi) {
+  uint64_t acc = op == LSB_REDUCE_SUM ? 0 : op == LSB_REDUCE_MIN ? ~0ull : 0ull;  // the encoding's identity
+  for (int64_t i = lo; i < hi; ++i) {
+    const uint64_t e = op == LSB_REDUCE_SUM ? value_at(i) : lsb_key_encode(value_at(i), val_type, 0);
+    acc = op == LSB_REDUCE_SUM ? acc + e : op == LSB_REDUCE_MIN ? std::min(acc, e) : std::max(acc, e);
+  }
+  return op == LSB_REDUCE_SUM ? acc : lsb_key_decode(acc, val_type, 0);
+}
+
+static void tails_case(const std::vector<uint64_t>& a, int P, const std::vector<uint64_t>& sum) {
+  const int64_t n = (int64_t)a.size(), per = lsb_per_rank(n, P);
+  const int forms[][2] = {{LSB_REDUCE_SUM, LSB_KEY_U64}, {LSB_REDUCE_MIN, LSB_KEY_I64}, {LSB_REDUCE_MAX, LSB_KEY_F64}};
+  for (const auto& f : forms) {
+    std::vector<uint64_t> lead(P, 0xDEADull), tail(P, 0xBEEFull);
+    for (int s = 0; s < P; ++s) {
+      const int64_t lo = s * per;
+      if (lsb_here(n, P, s) > 0 && lo > 0 && a[(size_t)lo] == a[(size_t)(lo - 1)])
+        lead[s] = fold_values(f[0], f[1], lo, lo + (int64_t)sum[(size_t)s * 4 + 3]);
+    }
+    CHECK(lsb_plan_run_tails(n, P, sum.data(), f[0], f[1], lead.data(), tail.data()) == LSB_OK, "plan_run_tails ok");
+    for (int r = 0; r < P; ++r) {
+      const int64_t here = lsb_here(n, P, r);
+      int64_t end = r * per + here;
+      while (here > 0 && end < n && a[(size_t)end] == a[(size_t)(end - 1)]) ++end;
+      CHECK(tail[r] == fold_values(f[0], f[1], r * per + here, here > 0 ? end : r * per + here),
+            "tail = the run's records on later ranks");
+    }
+  }
+}
+
 // lsb_plan_runs on the block partition of a[0..n) over P ranks: the summary
 // words from their definition, the plan against a walk over the whole array.
 static void runs_case(const std::vector<uint64_t>& a, int P) {
@@ -376,6 +421,7 @@ static void runs_case(const std::vector<uint64_t>& a, int P) {
     seen += mine;
   }
   CHECK(total == seen, "total");
+  tails_case(a, P, sum);
   // every corruption of a non-empty rank's words the header lists is refused
   for (int r = 0; r < P; ++r) {
     const uint64_t here = (uint64_t)lsb_here(n, P, r);
@@ -390,6 +436,9 @@ static void runs_case(const std::vector<uint64_t>& a, int P) {
       std::copy(b, b + 4, s2.begin() + (size_t)r * 4);
       CHECK(lsb_plan_runs(n, P, s2.data(), head0.data(), runs.data(), bases.data(), ends.data(), &total) ==
                 LSB_ERR_INVALID, "corrupted summary refused");
+      std::vector<uint64_t> lead(P, 0), tail(P, 0);
+      CHECK(lsb_plan_run_tails(n, P, s2.data(), LSB_REDUCE_SUM, LSB_KEY_U64, lead.data(), tail.data()) ==
+                LSB_ERR_INVALID, "corrupted summary refused by the tails too");
     }
   }
 }
@@ -430,6 +479,26 @@ static void runs_cases(std::mt19937_64& rng) {
             LSB_ERR_INVALID && t == -5, "store_runs: null ctx");
   CHECK(lsb_store_runs(nullptr, -1, -1, nullptr, 6, 2, nullptr, (int64_t*)col, nullptr, 3, nullptr) ==
             LSB_ERR_INVALID, "store_runs: all bad");
+  // the tails' planner: arguments, and the float sum's identity
+  std::vector<uint64_t> ld(2, 0), tl(2, 7);
+  s[3] = s[7] = 1;  // n = 2 over 2 ranks: one record each
+  CHECK(lsb_plan_run_tails(2, 2, s.data(), LSB_REDUCE_SUM, LSB_KEY_U64, ld.data(), tl.data()) == LSB_OK, "tails ok");
+  CHECK(lsb_plan_run_tails(2, 2, nullptr, 0, 0, ld.data(), tl.data()) == LSB_ERR_INVALID, "tails: null summary");
+  CHECK(lsb_plan_run_tails(2, 2, s.data(), 0, 0, nullptr, tl.data()) == LSB_ERR_INVALID, "tails: null lead");
+  CHECK(lsb_plan_run_tails(2, 2, s.data(), 0, 0, ld.data(), nullptr) == LSB_ERR_INVALID, "tails: null tail");
+  CHECK(lsb_plan_run_tails(-1, 2, s.data(), 0, 0, ld.data(), tl.data()) == LSB_ERR_INVALID, "tails: n < 0");
+  CHECK(lsb_plan_run_tails(2, 0, s.data(), 0, 0, ld.data(), tl.data()) == LSB_ERR_INVALID, "tails: P = 0");
+  CHECK(lsb_plan_run_tails(2, 65, s.data(), 0, 0, ld.data(), tl.data()) == LSB_ERR_INVALID, "tails: P = 65");
+  CHECK(lsb_plan_run_tails(2, 2, s.data(), 3, 0, ld.data(), tl.data()) == LSB_ERR_INVALID, "tails: op 3");
+  CHECK(lsb_plan_run_tails(2, 2, s.data(), 0, LSB_KEY_U32, ld.data(), tl.data()) == LSB_ERR_INVALID, "tails: u32");
+  const uint64_t neg0 = 0x8000000000000000ull;
+  ld[1] = neg0;  // both records carry key 0: rank 1's lead continues rank 0's run
+  CHECK(lsb_plan_run_tails(2, 2, s.data(), LSB_REDUCE_SUM, LSB_KEY_F64, ld.data(), tl.data()) == LSB_OK &&
+            tl[0] == neg0 && tl[1] == neg0, "a chain of -0.0 sums to -0.0, the identity");
+  CHECK(lsb_plan_reduce(nullptr, LSB_REDUCE_SUM, LSB_KEY_U64) == LSB_ERR_INVALID, "plan_reduce: null ctx");
+  t = -5;
+  CHECK(lsb_store_reduce(nullptr, 0, 4, col, &t) == LSB_ERR_INVALID && t == -5, "store_reduce: null ctx");
+  CHECK(lsb_store_reduce(nullptr, -1, -1, nullptr, nullptr) == LSB_ERR_INVALID, "store_reduce: all bad");
 }
 
 static int noop_ag(void*, const void*, void*, size_t) { return 0; }
