@@ -510,4 +510,18 @@ hipError_t launch_run_reduce(const Elem* A, int64_t here, int head0, const uint3
                              const int64_t* tile_base, int op, int val_type, uint64_t tail, uint64_t* tile_lead,
                              uint64_t* out, int64_t runs, uint32_t* err, hipStream_t s);
 
+// A run id per record (lsb_label_runs, include/lsb.h).  One
+// more read of A after launch_run_count and one write of B (another buffer of
+// at least `here` records): B[i] = {A[i].key, id} (kLabelKeep) or
+// {A[i].val, id} (kLabelByValue), id = gid0 + the heads of the rank at or
+// below i (position 0 among them exactly when head0) - 1: the index
+// launch_run_write gives the run that holds position i, plus gid0, the global
+// index of the rank's first run (>= 1 when head0 is 0: the records in front
+// of the first head get gid0 - 1).  A tile whose heads are not the tile_cnt[t]
+// of the count sets *err and writes nothing.  hipErrorInvalidValue on an
+// unknown mode, before any launch.
+constexpr int kLabelKeep = 0, kLabelByValue = 1;  // == LSB_LABEL_*
+hipError_t launch_run_label(const Elem* A, Elem* B, int64_t here, int64_t gid0, int head0, const uint32_t* tile_cnt,
+                            const int64_t* tile_base, int mode, uint32_t* err, hipStream_t s);
+
 }  // namespace lsb

@@ -11,7 +11,8 @@
 //   lsb_wholekey.cpp  the whole-key exchange (splitter search, one all-to-all,
 //                     merge of the P runs)
 //   lsb_runs.cpp      runs of equal keys (lsb_plan_runs, lsb_count_runs,
-//                     lsb_store_runs)
+//                     lsb_store_runs, lsb_plan_reduce, lsb_store_reduce,
+//                     lsb_label_runs)
 //   lsb_abi.cpp       the extern "C" entry points and the host planners
 //   lsb_xgeom.h       host-only exchange geometry (checked plan, waves); no
 //                     device header, so host tools can include it alone
@@ -361,8 +362,8 @@ void free_rank(Rank& r, const lsb_ctx* c = nullptr);
 int teardown_check(const lsb_ctx* c, const Rank& freeing);
 Rank* local_rank(lsb_ctx* c, int rank);
 int check_ctx(const lsb_ctx* c);
-// A is about to change: lsb_store_runs needs a new lsb_count_runs,
-// lsb_store_reduce a new lsb_plan_reduce after it.
+// A is about to change: lsb_store_runs and lsb_label_runs need a new
+// lsb_count_runs, lsb_store_reduce a new lsb_plan_reduce after it.
 inline void runs_invalidate(lsb_ctx* c) { c->runs_valid = c->reduce_valid = false; }
 // A caller's column of cnt elements of `elem` bytes at p, before a kernel may
 // touch it (lsb_context.cpp): LSB_ERR_INVALID unless it is aligned to its element,

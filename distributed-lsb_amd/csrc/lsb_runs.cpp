@@ -1,7 +1,8 @@
 // Runs of equal keys (include/lsb.h): the host planner over
 // the ranks' summary words, the collective count and the local store; and the
 // reductions over the runs' values (§7.3): the host planner over the ranks'
-// leading runs, the collective plan and the local store.
+// leading runs, the collective plan and the local store; and the run id of
+// every record (§7.4): one local call over the run plan.
 #include "lsb_keyform.h"
 #include "lsb_rt.h"
 
@@ -101,6 +102,33 @@ int gather_summaries(lsb_ctx* c, std::vector<uint64_t>& sum) {
   LSB_TRY(coll_allgather_u64(c, r, d + (size_t)r.rank * 4, d, 4));
   HIP_TRY(hipMemcpyAsync(sum.data(), d, sizeof(uint64_t) * 4 * P, hipMemcpyDeviceToHost, r.stream));
   HIP_TRY(hipStreamSynchronize(r.stream));
+  return LSB_OK;
+}
+
+// lsb_label_runs' work: every non-empty local rank's A -> B on its own
+// stream, then every rank's error word; the ranks swap only when none of
+// them found A changed.
+int label_ranks(lsb_ctx* c, int mode) {
+  for (Rank& r : c->ranks) {
+    if (r.here == 0) continue;
+    HIP_TRY(hipSetDevice(r.dev));
+    uint32_t* err = reinterpret_cast<uint32_t*>(r.run_sum + 4);
+    HIP_TRY(hipMemsetAsync(err, 0, sizeof(uint64_t), r.stream));
+    HIP_TRY(lsb::launch_run_label(r.A, r.B, r.here, c->run_base[r.rank], c->run_head0[r.rank], r.run_cnt,
+                                  r.run_tbase, mode, err, r.stream));
+  }
+  uint32_t any = 0;
+  for (Rank& r : c->ranks) {
+    if (r.here == 0) continue;
+    HIP_TRY(hipSetDevice(r.dev));
+    uint32_t h = 0;
+    HIP_TRY(hipMemcpyAsync(&h, r.run_sum + 4, sizeof h, hipMemcpyDeviceToHost, r.stream));
+    HIP_TRY(hipStreamSynchronize(r.stream));
+    any |= h;
+  }
+  if (any) return fail(LSB_ERR_STATE, "lsb_label_runs", "A changed since lsb_count_runs: no rank was labelled");
+  for (Rank& r : c->ranks)
+    if (r.here > 0) std::swap(r.A, r.B);
   return LSB_OK;
 }
 
@@ -228,6 +256,17 @@ int lsb_store_runs(lsb_ctx_t* c, int rank, int64_t cap, void* keys_dev, int key_
     return fail(LSB_ERR_STATE, where, "A changed since lsb_count_runs: the outputs are unspecified");
   }
   return LSB_OK;
+}
+
+int lsb_label_runs(lsb_ctx_t* c, int mode) {
+  const char* where = "lsb_label_runs";
+  LSB_TRY(check_ctx(c));
+  if (mode != LSB_LABEL_KEEP && mode != LSB_LABEL_BY_VALUE) return fail(LSB_ERR_INVALID, where, "mode");
+  if (!c->runs_valid) return fail(LSB_ERR_STATE, where, "no valid plan: call lsb_count_runs after the last change of A");
+  // The records change (or a rank found them changed already): the plans end here either way.
+  const int rc = c->n > 0 ? label_ranks(c, mode) : LSB_OK;
+  runs_invalidate(c);
+  return rc;
 }
 
 int lsb_plan_run_tails(int64_t n_total, int num_ranks, const uint64_t* summary, int op, int val_type,

@@ -14,8 +14,11 @@
 //   k_run_carry  one workgroup: the later tiles' leads and the later ranks'
 //                tail into the runs that go on past their tile
 //   k_run_lead, k_run_lead_sum  the values of a rank's leading run
-// No workgroup waits for another: a tile's base is ready before k_run_write
-// or k_run_reduce starts, every tile's lead before k_run_carry does.  No
+// and the run id of every record (lsb_label_runs):
+//   k_run_label  one more read of A and one write of B: every record with
+//                the global index of its run
+// No workgroup waits for another: a tile's base is ready before k_run_write,
+// k_run_reduce or k_run_label starts, every tile's lead before k_run_carry does.  No
 // floating-point atomics: the order of every addition is the code's.
 // Positions, bases and counts are 64-bit throughout.
 #include "lsb_kernels.h"
@@ -221,6 +224,73 @@ __global__ __launch_bounds__(kRunBlock) void k_run_write(const Elem* __restrict_
           if (starts) starts[h] = gbase + wave0 + j * 64 + lane;
           if (val_bytes == 8) static_cast<uint64_t*>(firsts)[h] = val[j];
           if (val_bytes == 4) static_cast<uint32_t*>(firsts)[h] = (uint32_t)val[j];
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// Build knob for experiments: 1 stores k_run_label's records nontemporally.
+#ifndef LSB_LABEL_NT
+#define LSB_LABEL_NT 0
+#endif
+typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
+
+// B[i] = {A[i].key (kLabelKeep) or A[i].val (kLabelByValue), id}, id = the global index
+// of the run that holds position i: gid0 + the rank's heads at or below i
+// (position 0 among them when head0) - 1, so the records in front of the
+// rank's first head, which belong to an earlier rank's run, get gid0 - 1.
+// k_run_write's tile shape and head numbering, with the heads *at or below*
+// the lane where a head there counts those below it.  Every record is stored
+// whole, at the position it was loaded from: each store instruction writes
+// 1 KiB of adjacent records, like the loads.  Plain stores.
+// A and B are different buffers: a wave reads A[wave0 - 1], another wave's
+// record.  The recount guards every store of the tile, as in k_run_write.
+template <int MODE>
+__global__ __launch_bounds__(kRunBlock) void k_run_label(const Elem* __restrict__ A, Elem* __restrict__ B,
+                                                         int64_t here, int64_t tiles, int64_t gid0, uint32_t head0,
+                                                         const uint32_t* __restrict__ tile_cnt,
+                                                         const int64_t* __restrict__ tile_base,
+                                                         uint32_t* __restrict__ err) {
+  __shared__ uint32_t s_cell[kRunCells];
+  __shared__ uint32_t s_total;
+  const int lane = run_lane(), wave = (int)(threadIdx.x >> 6);
+  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    uint64_t key[kRunItems], val[kRunItems], heads[kRunItems];
+    const int64_t wave0 = tile * kTile + (int64_t)wave * kRunWaveRecs;
+    // kLabelKeep drops the old value, and still loads whole records (as k_run_count)
+    wave_heads<MODE != kLabelKeep>(A, here, wave0, head0 != 0, key, val, heads);
+#pragma unroll
+    for (int j = 0; j < kRunItems; ++j)
+      if (lane == j) s_cell[wave * kRunItems + j] = (uint32_t)__popcll(heads[j]);
+    __syncthreads();
+    if (wave == 0) {  // cell counts -> exclusive prefixes, and their total
+      const uint32_t c = s_cell[lane];
+      uint32_t incl = c;
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t o = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += o;
+      }
+      s_cell[lane] = incl - c;
+      if (lane == 63) s_total = incl;
+    }
+    __syncthreads();
+    const uint32_t first = tile == 0 ? head0 : 0u;  // position 0 is the plan's, not the count's
+    if (s_total - first != tile_cnt[tile]) {
+      if (threadIdx.x == 0) atomicOr(err, 1u);
+    } else {
+      // the id of a record with no head of the tile at or below it
+      const int64_t id0 = gid0 + tile_base[tile] + (int64_t)(head0 - first) - 1;
+#pragma unroll
+      for (int j = 0; j < kRunItems; ++j) {
+        const int64_t i = wave0 + j * 64 + lane;
+        const uint32_t upto = s_cell[wave * kRunItems + j] + run_mbcnt(heads[j]) + (uint32_t)((heads[j] >> lane) & 1);
+        if (i < here) {
+          const u64x2 rec = {MODE == kLabelKeep ? key[j] : val[j], (uint64_t)(id0 + upto)};
+          if constexpr (LSB_LABEL_NT) __builtin_nontemporal_store(rec, reinterpret_cast<u64x2*>(B + i));
+          else *reinterpret_cast<u64x2*>(B + i) = rec;
         }
       }
     }
@@ -500,6 +570,23 @@ hipError_t launch_run_write(const Elem* A, int64_t here, int64_t gbase, int head
                      (uint32_t)head0, tile_cnt, tile_base, keys, key_type, flags, starts, firsts, val_bytes, err);
   if (counts)
     hipLaunchKernelGGL(k_run_diff, dim3(run_grid(runs, 256)), dim3(256), 0, s, starts, counts, runs, end);
+  return hipGetLastError();
+}
+
+hipError_t launch_run_label(const Elem* A, Elem* B, int64_t here, int64_t gid0, int head0, const uint32_t* tile_cnt,
+                            const int64_t* tile_base, int mode, uint32_t* err, hipStream_t s) {
+  if ((mode != kLabelKeep && mode != kLabelByValue) || (head0 != 0 && head0 != 1) || gid0 < 1 - head0 || !A || !B ||
+      A == B || !tile_cnt || !tile_base || !err)
+    return hipErrorInvalidValue;
+  if (here <= 0) return hipSuccess;
+  const int64_t tiles = run_tiles(here);
+  const dim3 grid(run_grid(tiles, 1)), block(kRunBlock);
+  if (mode == kLabelKeep)
+    hipLaunchKernelGGL(k_run_label<kLabelKeep>, grid, block, 0, s, A, B, here, tiles, gid0, (uint32_t)head0, tile_cnt,
+                       tile_base, err);
+  else
+    hipLaunchKernelGGL(k_run_label<kLabelByValue>, grid, block, 0, s, A, B, here, tiles, gid0, (uint32_t)head0,
+                       tile_cnt, tile_base, err);
   return hipGetLastError();
 }
 

@@ -23,7 +23,9 @@ keys, either order, values or argsort) uses ``sort(keys, values)``, or
 groups of equal keys come from ``unique(keys)``, or ``World.count_runs`` /
 ``World.store_runs`` after the sort, and one number per group from the value
 column (sum, min, max) from ``group_reduce(keys, values)``, or
-``World.plan_reduce`` / ``World.store_reduce``.  torch is imported only inside those
+``World.plan_reduce`` / ``World.store_reduce``, and the group of every record
+(unique's inverse, a dense rank) from ``unique(keys, return_inverse=True)`` or
+``dense_rank(keys)``, or ``World.label_runs``.  torch is imported only inside those
 functions.  A process that uses them imports torch before the first call into
 this module: the library then binds to the HIP runtime torch brought, and both
 see the same device memory.
@@ -76,6 +78,8 @@ KEY_U64, KEY_I64, KEY_F64, KEY_U32, KEY_I32, KEY_F32 = range(6)
 ORDER_DESCENDING = 1
 # Reductions over the runs' values (LSB_REDUCE_*).
 REDUCE_SUM, REDUCE_MIN, REDUCE_MAX = range(3)
+# What a labelled record becomes (LSB_LABEL_*): {key, id} or {old value, id}.
+LABEL_KEEP, LABEL_BY_VALUE = 0, 1
 
 
 class LsbError(RuntimeError):
@@ -194,6 +198,7 @@ def _lib() -> ctypes.CDLL:
             "lsb_plan_run_tails": (i32, [i64, i32, vp, i32, i32, vp, vp]),
             "lsb_plan_reduce": (i32, [vp, i32, i32]),
             "lsb_store_reduce": (i32, [vp, i32, i64, vp, P64]),
+            "lsb_label_runs": (i32, [vp, i32]),
             "lsb_sort": (i32, [vp]),
             "lsb_pass": (i32, [vp, i32]),
             "lsb_sync": (i32, [vp]),
@@ -377,17 +382,34 @@ def sort(keys, values=None, descending: bool = False, ranks: int = 1, radix_bits
     return out_k, out_v
 
 
+def _store_inverse(w, inverse) -> None:
+    """The run plan of w's sorted records, loaded with index values, into the
+    run id of every input record: label by value, sort by the index again,
+    store each rank's values into its block of `inverse` (int64, n)."""
+    w.label_runs(LABEL_BY_VALUE)
+    w.my_sort()
+    for r in range(w.P):
+        lo, h = r * w.per, w.here(r)
+        if h:
+            w.store_columns(r, None, inverse[lo:lo + h])
+
+
 def unique(keys, descending: bool = False, ranks: int = 1, radix_bits: int = 8,
-           key_type: Optional[int] = None):
-    """The distinct keys of a device column: (unique_keys, first_index, counts).
+           key_type: Optional[int] = None, return_inverse: bool = False):
+    """The distinct keys of a device column: (unique_keys, first_index, counts),
+    or with return_inverse=True (unique_keys, first_index, counts, inverse).
 
     unique_keys: the distinct keys in sorted order (descending: reversed), in
     the input's dtype; first_index: int64, the input index of each key's first
-    occurrence; counts: int64, how often it occurs.  Keys are equal when their
+    occurrence; counts: int64, how often it occurs; inverse: int64 of the
+    input's length, the index of each input key in unique_keys, so that
+    unique_keys[inverse] is the input bit for bit.  Keys are equal when their
     bits are: -0.0 and +0.0 are two keys, NaNs with different payloads too.
     keys as for sort(); the input is left untouched, the outputs are fresh
     tensors.  One World(n, ranks) loads the keys with index values, sorts,
-    counts the runs and stores each rank's into its part of the outputs."""
+    counts the runs and stores each rank's into its part of the outputs; the
+    inverse then labels every record with its run, sorts the records back by
+    their index and stores the labels."""
     import torch
     _check_column(keys, "keys")
     kt = _key_type_of(keys, key_type)
@@ -395,8 +417,9 @@ def unique(keys, descending: bool = False, ranks: int = 1, radix_bits: int = 8,
         raise ValueError("ranks")
     n = keys.numel()
     if n == 0:
-        return (torch.empty_like(keys), torch.empty(0, dtype=torch.int64, device=keys.device),
-                torch.empty(0, dtype=torch.int64, device=keys.device))
+        out = (torch.empty_like(keys), torch.empty(0, dtype=torch.int64, device=keys.device),
+               torch.empty(0, dtype=torch.int64, device=keys.device))
+        return out + (torch.empty(0, dtype=torch.int64, device=keys.device),) if return_inverse else out
     dev = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
     with World(n, ranks=ranks, devices=[dev] * ranks, radix_bits=radix_bits) as w:
         for r in range(ranks):
@@ -415,7 +438,40 @@ def unique(keys, descending: bool = False, ranks: int = 1, radix_bits: int = 8,
             if m:
                 w.store_runs(r, keys=out_k[lo:lo + m], starts=starts[lo:lo + m], counts=out_c[lo:lo + m],
                              firsts=out_i[lo:lo + m], descending=descending, key_type=kt)
+        if return_inverse:
+            inverse = torch.empty(n, dtype=torch.int64, device=keys.device)
+            _store_inverse(w, inverse)
+            return out_k, out_i, out_c, inverse
     return out_k, out_i, out_c
+
+
+def dense_rank(keys, descending: bool = False, ranks: int = 1, radix_bits: int = 8,
+               key_type: Optional[int] = None):
+    """The 0-based dense rank of every key of a device column: int64 of the
+    input's length, rank[i] = the number of distinct keys below keys[i]
+    (descending: above it), in the float order of lsb.h; equal keys (equal
+    bits) share a rank and the ranks have no gaps (SQL DENSE_RANK() - 1,
+    factorize codes of the sorted distinct keys, unique()'s inverse alone).
+    keys as for sort(); the input is left untouched."""
+    import torch
+    _check_column(keys, "keys")
+    kt = _key_type_of(keys, key_type)
+    if ranks < 1:
+        raise ValueError("ranks")
+    n = keys.numel()
+    inverse = torch.empty(n, dtype=torch.int64, device=keys.device)
+    if n == 0:
+        return inverse
+    dev = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
+    with World(n, ranks=ranks, devices=[dev] * ranks, radix_bits=radix_bits) as w:
+        for r in range(ranks):
+            lo, h = r * w.per, w.here(r)
+            if h:
+                w.load_columns(r, keys[lo:lo + h], None, descending=descending, key_type=kt)
+        w.my_sort()
+        w.count_runs()
+        _store_inverse(w, inverse)
+    return inverse
 
 
 def _value_type_of(t) -> int:
@@ -769,6 +825,14 @@ class World:
         runs = ctypes.c_int64()
         _check(_lib().lsb_store_reduce(self._h, rank, cap, out.data_ptr(), ctypes.byref(runs)), "lsb_store_reduce")
         return int(runs.value)
+
+    def label_runs(self, mode: int) -> None:
+        """lsb_label_runs: after count_runs, every record of every local rank
+        gets the global index of its run as its value: LABEL_KEEP leaves the
+        key, LABEL_BY_VALUE makes the old value the key (with index values, a
+        my_sort() after it puts the ids in input order: the inverse).  The
+        records change, so the plans end: count_runs again before a store."""
+        _check(_lib().lsb_label_runs(self._h, mode), "lsb_label_runs")
 
     def scatter_global(self, arr: np.ndarray) -> None:
         """Load a global array of n records into the block partition."""

@@ -361,7 +361,7 @@ int  lsb_store_columns(lsb_ctx_t* ctx, int rank, int64_t off, int64_t cnt,
  * every rank of the world.  n == 0: *total = 0, nothing is launched.  The
  * first call allocates 12 bytes per 4096 records of scratch on each rank.
  * The plan stays valid until lsb_generate, lsb_generate_ex, lsb_copy_in,
- * lsb_load_columns, lsb_sort or lsb_pass is called.  In a one-rank-per-
+ * lsb_load_columns, lsb_sort, lsb_pass or lsb_label_runs is called.  In a one-rank-per-
  * process world lsb_copy_in and lsb_load_columns are local calls and drop the
  * plan of the calling process only, while the other ranks' plans depend on
  * its records (a run's count reaches into later ranks): after any rank has
@@ -470,6 +470,50 @@ int  lsb_plan_run_tails(int64_t n_total, int num_ranks, const uint64_t* summary,
                         int op, int val_type, const uint64_t* lead, uint64_t* tail);
 int  lsb_plan_reduce(lsb_ctx_t* ctx, int op, int val_type);
 int  lsb_store_reduce(lsb_ctx_t* ctx, int rank, int64_t cap, void* out_dev, int64_t* runs);
+
+/* A run id per record: which group a row belongs to.  The calls above answer
+ * per run; this one labels every record with the global index of the run
+ * that holds it, id = bases[owner] + j, the index under which lsb_store_runs
+ * and lsb_store_reduce write that run.  It is the inverse of unique, the
+ * codes of factorize, DENSE_RANK() on a sorted array, a segment id, and the
+ * index that broadcasts a run's aggregate back to its records.
+ * For the record at slot i of rank r:
+ *   id = bases[r] + (the heads of rank r at or below i, slot 0 among them
+ *        exactly when head0[r]) - 1
+ * so the records of a leading run that began on an earlier rank (in front of
+ * the rank's first head, head0[r] == 0) get bases[r] - 1, and a rank that lies
+ * wholly inside one run (runs[r] == 0) gets that one id throughout.
+ *   LSB_LABEL_KEEP      the record becomes {key, id}: the order stays, the
+ *                       value is replaced
+ *   LSB_LABEL_BY_VALUE  the record becomes {key = its old value, value = id}
+ *
+ * lsb_label_runs: local, no collective; needs a valid run plan (LSB_ERR_STATE
+ * otherwise) and uses only what lsb_count_runs left behind.  One call labels
+ * every local rank of the context, each on its own stream, and returns when
+ * all of them are done.  It changes the records, so a successful call ends
+ * the run plan and the reduce plan like the calls lsb_count_runs lists; in a
+ * one-rank-per-process world every process calls it once, before the next
+ * collective.  An unknown mode returns LSB_ERR_INVALID before anything is
+ * launched and leaves the plan as it was.  n == 0 returns LSB_OK and launches
+ * nothing; empty local ranks launch nothing.
+ * Not in place: each rank's labelled records are written to its second record
+ * buffer, which then becomes A, as in a pass of the sort (the first buffer's
+ * contents are unspecified afterwards).  No scratch is allocated.
+ * LSB_ERR_STATE after the kernels: a local rank's A was changed behind the
+ * library's back since lsb_count_runs (a tile's heads differ from those
+ * counted).  Then no local rank is labelled, every A is what it was, and the
+ * plans are dropped.
+ * The inverse in input order: load the keys with lsb_load_columns and
+ * vals_dev NULL (the values are the global input indices), lsb_sort,
+ * lsb_count_runs, lsb_label_runs(LSB_LABEL_BY_VALUE), lsb_sort again.  Slot i
+ * of rank r then holds {r * per + i, the id of input record r * per + i}, and
+ * lsb_store_columns(keys_dev NULL, vals_dev, val_bytes 8 or 4) writes the
+ * rank's block of the inverse column.  The index keys are below n, so the
+ * second sort skips their constant upper digits.  The call does not check
+ * what the values are: with other values BY_VALUE sorts by those. */
+#define LSB_LABEL_KEEP     0
+#define LSB_LABEL_BY_VALUE 1
+int  lsb_label_runs(lsb_ctx_t* ctx, int mode);
 
 /* ---- the hot path ------------------------------------------------------- */
 /* == mySort(A, B): all 64/radix_bits passes; result in A.  Asynchronous

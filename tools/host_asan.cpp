@@ -20,7 +20,7 @@
 //   - the planner of the reductions over the runs' values
 //     (lsb_plan_run_tails) on the same partitions against a walk over the
 //     whole array; its refusals and identities; lsb_plan_reduce /
-//     lsb_store_reduce with a null context;
+//     lsb_store_reduce and lsb_label_runs with a null context;
 //   - lsb_create / lsb_create_rank_ops with no usable device: the failure
 //     path tears down a half-built context (no leak, no double free).
 #include <algorithm>
@@ -499,6 +499,8 @@ static void runs_cases(std::mt19937_64& rng) {
   t = -5;
   CHECK(lsb_store_reduce(nullptr, 0, 4, col, &t) == LSB_ERR_INVALID && t == -5, "store_reduce: null ctx");
   CHECK(lsb_store_reduce(nullptr, -1, -1, nullptr, nullptr) == LSB_ERR_INVALID, "store_reduce: all bad");
+  CHECK(lsb_label_runs(nullptr, LSB_LABEL_KEEP) == LSB_ERR_INVALID, "label_runs: null ctx");
+  CHECK(lsb_label_runs(nullptr, 2) == LSB_ERR_INVALID, "label_runs: null ctx, unknown mode");
 }
 
 static int noop_ag(void*, const void*, void*, size_t) { return 0; }
