@@ -302,6 +302,7 @@ int lsb_generate_ex(lsb_ctx_t* c, int dist, double param) {
     return fail(LSB_ERR_INVALID, "lsb_generate_ex", "dist");
   }
   runs_invalidate(c);
+  select_invalidate(c);
   c->keygen = g;
   for (Rank& r : c->ranks) {
     HIP_TRY(hipSetDevice(r.dev));
@@ -322,6 +323,7 @@ int lsb_copy_in(lsb_ctx_t* c, int rank, int64_t off, int64_t cnt, const lsb_elem
     return fail(LSB_ERR_INVALID, "lsb_copy_in", "rank or range");
   if (cnt == 0) return LSB_OK;
   runs_invalidate(c);
+  select_invalidate(c);
   HIP_TRY(hipSetDevice(r->dev));
   HIP_TRY(hipStreamSynchronize(r->stream));
   HIP_TRY(hipMemcpy(r->A + off, host, (size_t)cnt * sizeof(Elem), hipMemcpyHostToDevice));
@@ -374,6 +376,7 @@ int lsb_load_columns(lsb_ctx_t* c, int rank, int64_t off, int64_t cnt, const voi
   if (cnt == 0) return LSB_OK;
   if (!keys_dev) return fail(LSB_ERR_INVALID, "lsb_load_columns", "null keys");
   runs_invalidate(c);
+  select_invalidate(c);
   HIP_TRY(hipStreamSynchronize(r->stream));
   // The value of a record without one: its global index (mpi/mpi_lsbsort.cpp:650-656).
   const uint64_t val0 = (uint64_t)r->rank * (uint64_t)c->per + (uint64_t)off;
@@ -416,6 +419,7 @@ int lsb_pass(lsb_ctx_t* c, int digit) {
   LSB_TRY(check_ctx(c));
   if (digit < 0 || digit >= 64 / c->bits) return fail(LSB_ERR_INVALID, "lsb_pass", "digit");
   runs_invalidate(c);
+  select_invalidate(c);
   // Filed under the digit's own local passes (a 64-bit digit: the whole sort).
   c->pass_cursor = c->bits == 64 ? 0 : digit * (c->bits / lsb::kDigitBits);
   const int rc = do_pass(c, digit);
@@ -472,6 +476,7 @@ int lsb_sort(lsb_ctx_t* c) {
   if (c->broken)
     return fail(LSB_ERR_STATE, "lsb_sort", "an earlier sort failed and left packed records in A; load the input again");
   runs_invalidate(c);
+  select_invalidate(c);
   const int rc = sort_body(c);
   if (rc != LSB_OK) quiesce(c);
   return rc;

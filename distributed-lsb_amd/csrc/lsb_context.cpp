@@ -177,6 +177,10 @@ void free_rank(Rank& r, const lsb_ctx* c) {
   (void)hipFree(r.run_sum);
   (void)hipFree(r.run_lead);
   (void)hipFree(r.run_part);
+  (void)hipFree(r.sel_buf);
+  (void)hipFree(r.sel_gather);
+  (void)hipFree(r.sel_cnt);
+  (void)hipFree(r.sel_tbase);
   (void)hipFree(r.os_status);
   (void)hipFree(r.os_status2);
   (void)hipFree(r.rg_buf);

@@ -524,4 +524,39 @@ constexpr int kLabelKeep = 0, kLabelByValue = 1;  // == LSB_LABEL_*
 hipError_t launch_run_label(const Elem* A, Elem* B, int64_t here, int64_t gid0, int head0, const uint32_t* tile_cnt,
                             const int64_t* tile_base, int mode, uint32_t* err, hipStream_t s);
 
+// The k-th key and the first k + 1 records without a sort (lsb_select.hip;
+// lsb_select / lsb_store_select, include/lsb.h).
+// A rank's table of a round: kSelHist counts, then two words (round one: the
+// OR of the keys and the OR of their complements; later rounds: the records
+// the compaction reserved, and its error word); these kSelWords are what the
+// ranks gather.  The word after them is the store's error word.
+constexpr int kSelHist = 256;
+constexpr int kSelWords = kSelHist + 2;
+constexpr int kSelBufWords = kSelWords + 1;
+// One read of src[0, m) (m > 0): words[d] += the records with
+// (key & mask) == prefix whose byte at `shift` is d.  span: words[256] |= key,
+// words[257] |= ~key over every record (round one; mask is 0 then).  dst not
+// null: the matching records are also copied, whole and in any order, into
+// dst[0, bound); words[256] += the records reserved there, and a record past
+// `bound` is not stored and sets words[257].  dst and src do not overlap.
+hipError_t launch_select_hist(const Elem* src, int64_t m, int shift, uint64_t prefix, uint64_t mask, bool span,
+                              Elem* dst, int64_t bound, uint64_t* words, hipStream_t s);
+// One read of A (here > 0): tile_cnt[t] = (keys == pivot) << 16 | (keys <
+// pivot) of tile t (run_tiles(here) of them); tile_base[2 t], [2 t + 1] = the
+// keys below and equal in the tiles before t.  Totals other than `below` and
+// `equal` set *err.
+hipError_t launch_select_count(const Elem* A, int64_t here, uint64_t pivot, int64_t below, int64_t equal,
+                               uint32_t* tile_cnt, int64_t* tile_base, uint32_t* err, hipStream_t s);
+// One more read of A.  The record at slot i is selected when key < pivot, or
+// key == pivot and fewer than `share` equal keys lie in front of it; the j-th
+// selected record in slot order writes keys[j] = decode(key) and vals[j] = its
+// value (val_bytes 8) or its low word (4).  Either output may be null (vals
+// exactly when val_bytes is 0), not both.  take = below + share: no index
+// leaves [0, take); a record that would sets *err, and so does a tile whose
+// counts are not the tile_cnt[t] of the count, which then writes nothing.
+// Columns aligned to 16 bytes are written in 16-byte accesses.
+hipError_t launch_select_write(const Elem* A, int64_t here, uint64_t pivot, int64_t share, int64_t take,
+                               const uint32_t* tile_cnt, const int64_t* tile_base, void* keys, int key_type, int flags,
+                               void* vals, int val_bytes, uint32_t* err, hipStream_t s);
+
 }  // namespace lsb

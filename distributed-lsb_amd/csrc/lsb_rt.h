@@ -13,6 +13,8 @@
 //   lsb_runs.cpp      runs of equal keys (lsb_plan_runs, lsb_count_runs,
 //                     lsb_store_runs, lsb_plan_reduce, lsb_store_reduce,
 //                     lsb_label_runs)
+//   lsb_select.cpp    the k-th key and the first k + 1 records without a sort
+//                     (lsb_plan_select, lsb_select, lsb_store_select)
 //   lsb_abi.cpp       the extern "C" entry points and the host planners
 //   lsb_xgeom.h       host-only exchange geometry (checked plan, waves); no
 //                     device header, so host tools can include it alone
@@ -159,6 +161,11 @@ struct Rank {
   uint64_t* run_sum = nullptr;          // [kRunSumWords] summary words, k_run_write's error word
   uint64_t* run_lead = nullptr;         // [run_tiles(here)] k_run_reduce's tile leads (lsb_plan_reduce)
   uint64_t* run_part = nullptr;         // [kRunLeadParts + 1] k_run_lead's partials, then the leading run's word
+  // The select (lsb_select.cpp), allocated on first use.
+  uint64_t* sel_buf = nullptr;          // [kSelBufWords] a round's table, then lsb_store_select's error word
+  uint64_t* sel_gather = nullptr;       // [P][kSelWords] all-gathered tables (one rank per process)
+  uint32_t* sel_cnt = nullptr;          // [run_tiles(here)] keys below and equal to the pivot per tile (k_sel_count)
+  int64_t* sel_tbase = nullptr;         // [run_tiles(here)][2] those of the tiles before (k_sel_scan)
   std::vector<int64_t> send_counts, send_displs, recv_counts, recv_displs;
 };
 
@@ -216,6 +223,15 @@ struct lsb_ctx {
   bool reduce_valid = false;
   int reduce_op = 0, reduce_type = 0;
   std::vector<uint64_t> run_tail;                     // [P]
+  // The plan of the last lsb_select (lsb_plan_select over every rank's
+  // counts), valid until an entry point that can change A (select_invalidate);
+  // the run plan and this one do not end each other.  What that call ran
+  // outlives the plan (lsb_get_last_select).
+  bool select_valid = false;
+  uint64_t sel_pivot = 0;
+  std::vector<int64_t> sel_below, sel_equal, sel_take, sel_base;  // [P]
+  int sel_rounds = 0;
+  int64_t sel_read = 0;
   lsb::KeyGen keygen;
   std::vector<lsb_rt::PendingEvent> pending;
   std::vector<std::pair<int, hipEvent_t>> event_pool;  // (device, event) of finished timings
@@ -365,6 +381,8 @@ int check_ctx(const lsb_ctx* c);
 // A is about to change: lsb_store_runs and lsb_label_runs need a new
 // lsb_count_runs, lsb_store_reduce a new lsb_plan_reduce after it.
 inline void runs_invalidate(lsb_ctx* c) { c->runs_valid = c->reduce_valid = false; }
+// A is about to change: lsb_store_select needs a new lsb_select.
+inline void select_invalidate(lsb_ctx* c) { c->select_valid = false; }
 // A caller's column of cnt elements of `elem` bytes at p, before a kernel may
 // touch it (lsb_context.cpp): LSB_ERR_INVALID unless it is aligned to its element,
 // device (or managed) memory of the rank's device and inside its allocation.

@@ -266,6 +266,7 @@ int lsb_label_runs(lsb_ctx_t* c, int mode) {
   // The records change (or a rank found them changed already): the plans end here either way.
   const int rc = c->n > 0 ? label_ranks(c, mode) : LSB_OK;
   runs_invalidate(c);
+  select_invalidate(c);
   return rc;
 }
 

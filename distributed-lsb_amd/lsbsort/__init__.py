@@ -25,7 +25,9 @@ groups of equal keys come from ``unique(keys)``, or ``World.count_runs`` /
 column (sum, min, max) from ``group_reduce(keys, values)``, or
 ``World.plan_reduce`` / ``World.store_reduce``, and the group of every record
 (unique's inverse, a dense rank) from ``unique(keys, return_inverse=True)`` or
-``dense_rank(keys)``, or ``World.label_runs``.  torch is imported only inside those
+``dense_rank(keys)``, or ``World.label_runs``.  The k-th key and the k best
+records need no sort: ``kth(keys, k)`` and ``topk(keys, k)``, or ``World.select`` /
+``World.store_select``.  torch is imported only inside those
 functions.  A process that uses them imports torch before the first call into
 this module: the library then binds to the HIP runtime torch brought, and both
 see the same device memory.
@@ -199,6 +201,10 @@ def _lib() -> ctypes.CDLL:
             "lsb_plan_reduce": (i32, [vp, i32, i32]),
             "lsb_store_reduce": (i32, [vp, i32, i64, vp, P64]),
             "lsb_label_runs": (i32, [vp, i32]),
+            "lsb_plan_select": (i32, [i64, i32, i64, vp, vp, vp, vp]),
+            "lsb_select": (i32, [vp, i64, ctypes.POINTER(ctypes.c_uint64), P64, P64, vp, vp]),
+            "lsb_store_select": (i32, [vp, i32, i64, vp, i32, i32, vp, i32, P64]),
+            "lsb_get_last_select": (i32, [vp, ctypes.POINTER(ctypes.c_int), P64]),
             "lsb_sort": (i32, [vp]),
             "lsb_pass": (i32, [vp, i32]),
             "lsb_sync": (i32, [vp]),
@@ -534,6 +540,105 @@ def group_reduce(keys, values, op: str = "sum", descending: bool = False, ranks:
     return out_k, out_v
 
 
+def _key_tensor(bits: int, like):
+    """A 1-element tensor of like's dtype and device whose bits are `bits`."""
+    import torch
+    wide = like.element_size() == 8
+    width = 64 if wide else 32
+    bits &= (1 << width) - 1
+    signed = bits - (1 << width) if bits >> (width - 1) else bits
+    t = torch.tensor([signed], dtype=torch.int64 if wide else torch.int32, device=like.device)
+    return t.view(like.dtype)
+
+
+def kth(keys, k: int, descending: bool = False, ranks: int = 1, radix_bits: int = 8,
+        key_type: Optional[int] = None):
+    """The k-th smallest key of a device column (descending: the k-th
+    largest), k counted from 0: (value, below, equal).
+
+    value: a 1-element tensor of the keys' dtype on their device, the key the
+    stable sort would put at position k, bit for bit (NaN payloads, the sign
+    of zero); below, equal: how many keys lie before it in the order and how
+    many have its bits, so below <= k < below + equal.  The order is sort()'s
+    (lsb.h's float order).  No sort is run: one World(n, ranks) loads the keys
+    and selects.  keys as for sort(); the input is left untouched.
+    ValueError unless 0 <= k < len(keys)."""
+    import torch
+    _check_column(keys, "keys")
+    kt = _key_type_of(keys, key_type)
+    if ranks < 1:
+        raise ValueError("ranks")
+    n = keys.numel()
+    if not 0 <= k < n:
+        raise ValueError(f"k = {k} outside [0, {n})")
+    dev = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
+    with World(n, ranks=ranks, devices=[dev] * ranks, radix_bits=radix_bits) as w:
+        for r in range(ranks):
+            lo, h = r * w.per, w.here(r)
+            if h:
+                w.load_columns(r, keys[lo:lo + h], None, descending=descending, key_type=kt)
+        plan = w.select(k)
+    return _key_tensor(key_decode(plan["key"], kt, descending), keys), plan["below"], plan["equal"]
+
+
+def topk(keys, k: int, largest: bool = True, sorted: bool = True, ranks: int = 1, radix_bits: int = 8,  # noqa: A002
+         key_type: Optional[int] = None):
+    """The k largest keys of a device column (largest=False: the k smallest)
+    and where they were: (values, indices), the first k records of the stable
+    sort in that direction, so among equal keys the lowest input indices are
+    taken (a rule torch.topk does not promise).
+
+    values: the keys' dtype, bit for bit; indices: int64 input indices.
+    sorted=True gives them in the sort's order (sort() over the k records),
+    sorted=False in input order.  The order is sort()'s (lsb.h's float order:
+    NaNs with the sign clear are the largest).  One World(n, ranks) loads the
+    keys with index values, selects position k - 1 and stores each rank's part
+    of the selection; no full sort is run.  keys as for sort(); the input is
+    left untouched.  k == 0 or no keys: empty tensors; k > len(keys):
+    ValueError."""
+    import torch
+    _check_column(keys, "keys")
+    kt = _key_type_of(keys, key_type)
+    if ranks < 1:
+        raise ValueError("ranks")
+    n = keys.numel()
+    if k < 0 or k > n:
+        raise ValueError(f"k = {k} outside [0, {n}]")
+    values = torch.empty(k, dtype=keys.dtype, device=keys.device)
+    indices = torch.empty(k, dtype=torch.int64, device=keys.device)
+    if k == 0:
+        return values, indices
+    dev = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
+    with World(n, ranks=ranks, devices=[dev] * ranks, radix_bits=radix_bits) as w:
+        for r in range(ranks):
+            lo, h = r * w.per, w.here(r)
+            if h:
+                w.load_columns(r, keys[lo:lo + h], None, descending=largest, key_type=kt)
+        plan = w.select(k - 1)
+        for r in range(ranks):
+            lo, m = plan["bases"][r], plan["take"][r]
+            if m:
+                w.store_select(r, values[lo:lo + m], indices[lo:lo + m], descending=largest, key_type=kt)
+    if sorted:
+        return sort(values, indices, descending=largest, radix_bits=radix_bits, key_type=kt)
+    return values, indices
+
+
+def plan_select(n: int, P: int, count: int, below: np.ndarray, equal: np.ndarray) -> dict:
+    """lsb_plan_select, the host planner of the select: below[r], equal[r] =
+    rank r's records below and equal to the pivot, count = k + 1 wanted
+    records -> {"take", "bases"} (P each): what each rank gives and where its
+    part starts."""
+    below = np.ascontiguousarray(below, dtype=np.int64)
+    equal = np.ascontiguousarray(equal, dtype=np.int64)
+    if below.shape != (P,) or equal.shape != (P,):
+        raise ValueError("below and equal must hold P entries")
+    out = {k: np.zeros(P, dtype=np.int64) for k in ("take", "bases")}
+    _check(_lib().lsb_plan_select(n, P, count, below.ctypes.data, equal.ctypes.data, out["take"].ctypes.data,
+                                  out["bases"].ctypes.data), "lsb_plan_select")
+    return out
+
+
 def plan_runs(n: int, P: int, summary: np.ndarray) -> dict:
     """lsb_plan_runs, the host planner of the runs of equal keys: summary is
     P x 4 uint64 (first key, last key, inner heads, leading run's length of
@@ -833,6 +938,58 @@ class World:
         my_sort() after it puts the ids in input order: the inverse).  The
         records change, so the plans end: count_runs again before a store."""
         _check(_lib().lsb_label_runs(self._h, mode), "lsb_label_runs")
+
+    def select(self, k: int) -> dict:
+        """lsb_select: the key the stable sort would put at global position k
+        and the plan of the first k + 1 records, without sorting (a collective
+        in a one-rank-per-process world; every A stays as it is, every B is
+        scratch).  {"key": the mapped uint64 key (key_decode gives the typed
+        bits), "below", "equal": records of the array below and equal to it,
+        "take": [P] records each rank gives, "bases": [P] where each rank's
+        part starts}; store_select needs it, after the last change of the
+        records."""
+        key = ctypes.c_uint64()
+        below, equal = ctypes.c_int64(), ctypes.c_int64()
+        take = np.zeros(self.P, dtype=np.int64)
+        bases = np.zeros(self.P, dtype=np.int64)
+        _check(_lib().lsb_select(self._h, k, ctypes.byref(key), ctypes.byref(below), ctypes.byref(equal),
+                                 take.ctypes.data, bases.ctypes.data), "lsb_select")
+        return {"key": int(key.value), "below": int(below.value), "equal": int(equal.value),
+                "take": [int(x) for x in take], "bases": [int(x) for x in bases]}
+
+    def store_select(self, rank: int, keys=None, values=None, descending: bool = False,
+                     key_type: Optional[int] = None, val_bytes: Optional[int] = None) -> int:
+        """lsb_store_select: `rank`'s part of the selection into device columns
+        (1-D contiguous CUDA torch tensors, either may be None), in slot
+        order: keys with the key type and order the load was given, values any
+        4- or 8-byte dtype (4: the value's low word; val_bytes= overrides the
+        element size).  Every column holds at least the rank's part; -> its
+        length."""
+        import torch
+        cols = [(t, what) for t, what in ((keys, "keys"), (values, "values")) if t is not None]
+        if not cols:
+            raise ValueError("no output column")
+        for t, what in cols:
+            _check_column(t, what, cols[0][0].device)
+        cap = min(t.numel() for t, _ in cols)
+        kt = _key_type_of(keys, key_type) if keys is not None else (KEY_U64 if key_type is None else key_type)
+        if cap == 0:  # an empty tensor has no address: stand-ins say which outputs are meant (cap 0: never written)
+            keys, values = (None if t is None else t.new_empty(1) for t in (keys, values))
+        vb, vp = (values.element_size() if val_bytes is None else val_bytes, values.data_ptr()) \
+            if values is not None else (0 if val_bytes is None else val_bytes, None)
+        torch.cuda.current_stream(cols[0][0].device).synchronize()
+        count = ctypes.c_int64()
+        _check(_lib().lsb_store_select(self._h, rank, cap, None if keys is None else keys.data_ptr(), kt,
+                                       ORDER_DESCENDING if descending else 0, vp, vb, ctypes.byref(count)),
+               "lsb_store_select")
+        return int(count.value)
+
+    def last_select(self) -> tuple:
+        """(histogram rounds, records read on the local ranks) of the last
+        select (lsb_get_last_select)."""
+        rounds, read = ctypes.c_int(), ctypes.c_int64()
+        _check(_lib().lsb_get_last_select(self._h, ctypes.byref(rounds), ctypes.byref(read)), "lsb_get_last_select")
+        return int(rounds.value), int(read.value)
 
     def scatter_global(self, arr: np.ndarray) -> None:
         """Load a global array of n records into the block partition."""

@@ -515,6 +515,99 @@ int  lsb_store_reduce(lsb_ctx_t* ctx, int rank, int64_t cap, void* out_dev, int6
 #define LSB_LABEL_BY_VALUE 1
 int  lsb_label_runs(lsb_ctx_t* ctx, int mode);
 
+/* ---- the k-th key and the first k + 1 records, without a sort -------------- */
+/* The commonest question that needs no full sort: the k-th smallest key
+ * (median, percentile, threshold) and the k best records (top-k with their
+ * input indices), across rank boundaries.
+ * The array is the global one: rank 0's slots, then rank 1's, ...  It may be
+ * in any order; sortedness is neither needed nor used.  Keys are the mapped
+ * unsigned 64-bit keys of lsb_key_encode: a descending load selects from the
+ * top, and floats follow the order given above.
+ * For 0 <= k < n let pivot be the key the stable sort would put at global
+ * position k, below the number of records with key < pivot and equal the
+ * number with key == pivot, so below <= k < below + equal.  The selection of
+ * k is the first k + 1 records of the stable sort, as a set: every record
+ * with key < pivot, and the first k + 1 - below records with key == pivot in
+ * global position order (with index values: the lowest input indices among
+ * the ties).
+ *
+ * lsb_plan_select: the host planner, pure host code.  count = k + 1 records
+ * are wanted; below[r] and equal[r] are rank r's records below and equal to
+ * the pivot.  With E = count - sum(below), rank r gives
+ * min(equal[r], max(0, E - sum of equal[s] over s < r)) of its equal records,
+ * the rule of lsb_plan_merge: equal keys keep rank order.  Out, P entries
+ * each: take[r] = below[r] + that; bases[r] = the exclusive prefix sum of
+ * take.  LSB_ERR_INVALID on a null argument, n < 0, P outside [1, 64], a
+ * negative entry, below[r] + equal[r] > here(r), or counts that do not
+ * bracket count: sum(below) < count <= sum(below) + sum(equal) is false.
+ *
+ * lsb_select: collective in one-rank-per-process contexts, like
+ * lsb_count_runs: every rank calls it with the same k.  An MSD radix select:
+ * a round reads each rank's candidates once and counts one key byte of those
+ * whose upper bits equal the prefix found so far; the ranks' 256 counts are
+ * gathered (258 words per rank), the bucket that holds the wanted rank is
+ * chosen and the buckets in front of it are added to below.  Round one reads
+ * A, takes the top byte and also reduces the span of the keys; a byte on
+ * which all keys of the array agree costs no round after that (all-equal keys
+ * finish after one read, 32-bit key types do their four upper bytes in round
+ * one).  A rank whose count in the chosen bucket is at most half of what its
+ * source holds copies those records into its B in the next round's read and
+ * reads only them from then on.
+ * Every A stays bit for bit as it was.  Each rank's B is scratch: its
+ * contents are unspecified afterwards, as after lsb_label_runs.
+ * *key = pivot, *below and *equal = the counts over the whole array; take[P]
+ * and bases[P] as lsb_plan_select gives them for count = k + 1, for every
+ * rank of the world.  Every output may be NULL.
+ * The context keeps the plan (pivot and the per-rank counts) until
+ * lsb_generate, lsb_generate_ex, lsb_copy_in, lsb_load_columns, lsb_sort,
+ * lsb_pass or lsb_label_runs is called: the calls that end a run plan, and
+ * the note on one-rank-per-process worlds there applies unchanged.  The run
+ * plan and the reduce plan are left alone, and lsb_count_runs,
+ * lsb_store_runs, lsb_plan_reduce and lsb_store_reduce leave this plan alone.
+ * LSB_ERR_INVALID, before anything is launched or gathered: null context, or
+ * k outside [0, n) (n == 0: every k).  LSB_ERR_STATE: an earlier sort left
+ * the context unusable (as lsb_sort), or the gathered counts are not those of
+ * an array (A was changed during the call).
+ * The first call allocates, on each rank, 259 + 258 P words of tables (the
+ * gather area only in one-rank-per-process contexts), freed with the context;
+ * nothing sized by the records.
+ *
+ * lsb_store_select: local, no collective; needs a select plan (LSB_ERR_STATE
+ * otherwise).  Reads rank's A twice more (counts per 4096-record tile, then
+ * the write) and writes the rank's part of the selection, take[rank] records,
+ * compacted, in slot order (not in key order: a caller that wants the k + 1
+ * records ordered sorts them): for the j-th selected record of the rank
+ *   keys_dev[j] = decode(key) with key_type and flags as lsb_store_columns
+ *   vals_dev[j] = the value (val_bytes 8) or its low word (val_bytes 4)
+ * Either output may be NULL (val_bytes 0 with vals_dev NULL), not both.
+ * cap = the elements every given output holds.  *count (may be NULL) =
+ * take[rank]; cap < take[rank] returns LSB_ERR_INVALID with *count set and
+ * nothing written.  A rank that takes nothing returns LSB_OK, launches
+ * nothing and does not examine the pointers.
+ * LSB_ERR_INVALID, before any kernel is launched: bad rank, cap < 0, unknown
+ * key type or flag bits, val_bytes not 0, 4 or 8 or disagreeing with
+ * vals_dev, no output, and for each output the pointer checks of
+ * lsb_load_columns over cap elements.  Columns aligned to 16 bytes are
+ * written in 16-byte accesses, others element by element, with equal results.
+ * LSB_ERR_STATE after the kernels: A was changed behind the library's back
+ * since lsb_select (a tile's counts differ on the second read, or the rank's
+ * totals are not the plan's); the outputs are then unspecified, nothing is
+ * written outside [0, take[rank]) and the plan is dropped.
+ * The first call allocates 20 bytes per 4096 records of scratch on the rank.
+ * Streams as lsb_store_runs.
+ *
+ * lsb_get_last_select: what the last lsb_select of the context ran: *rounds =
+ * its histogram rounds, each with its gather; *records_read = the records
+ * its kernels read on this context's local ranks, summed: reads of A and
+ * reads of candidates in B.  Either may be NULL. */
+int  lsb_plan_select(int64_t n_total, int num_ranks, int64_t count,
+                     const int64_t* below, const int64_t* equal, int64_t* take, int64_t* bases);
+int  lsb_select(lsb_ctx_t* ctx, int64_t k, uint64_t* key, int64_t* below, int64_t* equal,
+                int64_t* take, int64_t* bases);
+int  lsb_store_select(lsb_ctx_t* ctx, int rank, int64_t cap, void* keys_dev, int key_type, int flags,
+                      void* vals_dev, int val_bytes, int64_t* count);
+int  lsb_get_last_select(lsb_ctx_t* ctx, int* rounds, int64_t* records_read);
+
 /* ---- the hot path ------------------------------------------------------- */
 /* == mySort(A, B): all 64/radix_bits passes; result in A.  Asynchronous
  * with respect to the host except for the per-pass count exchange when

@@ -21,6 +21,9 @@
 //     (lsb_plan_run_tails) on the same partitions against a walk over the
 //     whole array; its refusals and identities; lsb_plan_reduce /
 //     lsb_store_reduce and lsb_label_runs with a null context;
+//   - the planner of the select (lsb_plan_select) for every k of random
+//     partitions against the stable sort of the whole array; its refusals;
+//     lsb_select / lsb_store_select with a null context and bad arguments;
 //   - lsb_create / lsb_create_rank_ops with no usable device: the failure
 //     path tears down a half-built context (no leak, no double free).
 #include <algorithm>
@@ -503,6 +506,64 @@ static void runs_cases(std::mt19937_64& rng) {
   CHECK(lsb_label_runs(nullptr, 2) == LSB_ERR_INVALID, "label_runs: null ctx, unknown mode");
 }
 
+// lsb_plan_select on the block partition of a[0..n) over P ranks for every k:
+// the counts from their definition, take against the first k + 1 positions of
+// the stable sort counted per rank.
+static void select_cases(std::mt19937_64& rng) {
+  for (int it = 0; it < 1500; ++it) {
+    const int64_t n = 1 + (int64_t)(rng() % 40);
+    const int P = 1 + (int)(rng() % 8), d = 1 + (int)(rng() % 5);
+    const int64_t per = lsb_per_rank(n, P);
+    std::vector<uint64_t> a((size_t)n);
+    for (auto& x : a) x = rng() % d;
+    std::vector<int64_t> order((size_t)n);
+    for (int64_t i = 0; i < n; ++i) order[(size_t)i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int64_t x, int64_t y) { return a[(size_t)x] < a[(size_t)y]; });
+    for (int64_t k = 0; k < n; ++k) {
+      const uint64_t pivot = a[(size_t)order[(size_t)k]];
+      std::vector<int64_t> below(P, 0), equal(P, 0), want(P, 0), take(P, -7), bases(P, -7);
+      for (int64_t i = 0; i < n; ++i) {
+        below[(size_t)(i / per)] += a[(size_t)i] < pivot;
+        equal[(size_t)(i / per)] += a[(size_t)i] == pivot;
+      }
+      for (int64_t j = 0; j <= k; ++j) ++want[(size_t)(order[(size_t)j] / per)];
+      CHECK(lsb_plan_select(n, P, k + 1, below.data(), equal.data(), take.data(), bases.data()) == LSB_OK,
+            "plan_select ok");
+      int64_t acc = 0;
+      for (int r = 0; r < P; ++r) {
+        CHECK(take[r] == want[r], "take = the rank's share of the first k + 1");
+        CHECK(bases[r] == acc, "bases are the prefix sums");
+        acc += take[r];
+      }
+      std::vector<int64_t> bad(below);
+      bad[rng() % P] = -1;
+      CHECK(lsb_plan_select(n, P, k + 1, bad.data(), equal.data(), take.data(), bases.data()) == LSB_ERR_INVALID,
+            "negative count refused");
+      bad = equal;
+      bad[0] = lsb_here(n, P, 0) - below[0] + 1;
+      CHECK(lsb_plan_select(n, P, k + 1, below.data(), bad.data(), take.data(), bases.data()) == LSB_ERR_INVALID,
+            "more keys than the rank holds refused");
+    }
+  }
+  std::vector<int64_t> b(2, 0), e(2, 1), o(2);
+  CHECK(lsb_plan_select(2, 2, 1, b.data(), e.data(), o.data(), o.data()) == LSB_OK, "plan_select: first of two");
+  CHECK(lsb_plan_select(2, 2, 0, b.data(), e.data(), o.data(), o.data()) == LSB_ERR_INVALID, "plan_select: count 0");
+  CHECK(lsb_plan_select(2, 2, 3, b.data(), e.data(), o.data(), o.data()) == LSB_ERR_INVALID, "plan_select: count 3");
+  CHECK(lsb_plan_select(2, 2, 1, nullptr, e.data(), o.data(), o.data()) == LSB_ERR_INVALID, "plan_select: null below");
+  CHECK(lsb_plan_select(2, 2, 1, b.data(), e.data(), nullptr, o.data()) == LSB_ERR_INVALID, "plan_select: null take");
+  CHECK(lsb_plan_select(-1, 2, 1, b.data(), e.data(), o.data(), o.data()) == LSB_ERR_INVALID, "plan_select: n < 0");
+  CHECK(lsb_plan_select(2, 65, 1, b.data(), e.data(), o.data(), o.data()) == LSB_ERR_INVALID, "plan_select: P = 65");
+  uint64_t col[4] = {0, 1, 2, 3}, key = 5;
+  int64_t t = -5;
+  CHECK(lsb_select(nullptr, 0, &key, &t, &t, o.data(), o.data()) == LSB_ERR_INVALID && key == 5 && t == -5,
+        "select: null ctx");
+  CHECK(lsb_store_select(nullptr, 0, 4, col, LSB_KEY_U64, 0, col, 8, &t) == LSB_ERR_INVALID && t == -5,
+        "store_select: null ctx");
+  CHECK(lsb_store_select(nullptr, -1, -1, nullptr, 6, 2, nullptr, 3, nullptr) == LSB_ERR_INVALID,
+        "store_select: all bad");
+  CHECK(lsb_get_last_select(nullptr, nullptr, nullptr) == LSB_ERR_INVALID, "last_select: null ctx");
+}
+
 static int noop_ag(void*, const void*, void*, size_t) { return 0; }
 static int noop_a2a(void*, const void*, const size_t*, const size_t*, void*, const size_t*,
                     const size_t*) { return 0; }
@@ -540,6 +601,7 @@ int main() {
   for (int code = 0; code < 8; ++code) CHECK(lsb_strerror(code) != nullptr, "strerror");
   keyform_case(rng);
   runs_cases(rng);
+  select_cases(rng);
   uint64_t col[4] = {0, 1, 2, 3};  // host memory: never reaches a device call with a null context
   CHECK(lsb_load_columns(nullptr, 0, 0, 4, col, LSB_KEY_U64, col, 8, 0) == LSB_ERR_INVALID, "load: null ctx");
   CHECK(lsb_store_columns(nullptr, 0, 0, 4, col, LSB_KEY_U64, col, 8, 0) == LSB_ERR_INVALID, "store: null ctx");
