@@ -438,6 +438,7 @@ int sort_body(lsb_ctx* c) {
   c->last_varying = ~0ull;
   c->last_first = LSB_FIRST_COUNT;
   c->last_records = LSB_RECORDS_FULL;
+  c->last_packed_tile = 0;
   c->pass_cursor = 0;
   c->cur_pass = 0;
   if (c->bits == 64 && exchanging(c)) {
@@ -501,6 +502,13 @@ int lsb_get_last_records(lsb_ctx_t* c, int* form) {
   LSB_TRY(check_ctx(c));
   if (!form) return fail(LSB_ERR_INVALID, "lsb_get_last_records", "null");
   *form = c->last_records;
+  return LSB_OK;
+}
+
+int lsb_get_last_packed_tile(lsb_ctx_t* c, int* records) {
+  LSB_TRY(check_ctx(c));
+  if (!records) return fail(LSB_ERR_INVALID, "lsb_get_last_packed_tile", "null");
+  *records = c->last_packed_tile;
   return LSB_OK;
 }
 

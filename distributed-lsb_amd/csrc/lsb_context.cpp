@@ -409,6 +409,12 @@ lsb_ctx* new_ctx(int64_t n_total, int num_ranks, int radix_bits) {
     const int v = atoi(e);
     if (v >= 0 && v <= 2) c->pack_values = v;
   }
+  // LSB_PACKED_TILE=4096|4608|5120: records per tile of a packed sort's middle
+  // passes (A/B runs and tests; sorts too small for it keep 4096).
+  if (const char* e = getenv("LSB_PACKED_TILE")) {
+    const int v = atoi(e);
+    if (lsb::onesweep_packed_tile_ok(v)) c->packed_tile = v;
+  }
   // LSB_EXCHANGE_CHUNKS=C: contexts start with LSB_OPT_EXCHANGE_CHUNKS = C
   // (A/B runs of programs that do not set options); LSB_XCHUNK_RESERVE: the
   // chunk passes' grid leaves that many workgroups to the wire (experiments).

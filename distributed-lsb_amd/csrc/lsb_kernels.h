@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "lsb_keyform.h"
+#include "lsb_ostile.h"
 
 namespace lsb {
 
@@ -103,14 +104,30 @@ hipError_t launch_starts_to_counts(const int64_t* first16, int64_t m, uint64_t* 
                                    hipStream_t s);
 
 // Single-read passes (P == 1; k_onesweep in lsb_kernels.hip).  The m records
-// are kTile-record tiles in kOnesweepSubs contiguous sub-arrays, sub-array x
+// are kTile-record tiles (a packed sort's middle passes: kOsTile10, below) in
+// kOnesweepSubs contiguous sub-arrays (lsb_ostile.h), sub-array x
 // = tiles [x*TT/8, (x+1)*TT/8).  sub_hist[x * 256 + b] = count of digit b
 // in sub-array x.
-constexpr int kOnesweepSubs = 8;
 // Look-back values are 30 bits (a bucket's count within one sub-array of
 // m / 8 + kTile records): m < 2^33 - 2^16, i.e. 137 GB per record buffer.
 constexpr int64_t kOnesweepMaxElems = (int64_t(1) << 33) - (int64_t(1) << 16);
 inline int64_t onesweep_tiles(int64_t m) { return (m + kTile - 1) / kTile; }
+// The packed middle passes (Packed -> Packed counting the next digit, no
+// regional layout) may take larger tiles: their stage costs 12 bytes per
+// record, so 512 threads x 10 records still fit two workgroups per CU
+// (kOsTile10; kOsTile9 is the size between, for measurements).  Every other
+// instance keeps kTile.  A pass counts the next digit per sub-array of the
+// next pass's input, so it is told the next pass's tile size (tn) as well as
+// its own (t).
+constexpr int kOsTile9 = kOsBlock * 9;    // 4608
+constexpr int kOsTile10 = kOsBlock * 10;  // 5120
+inline bool onesweep_packed_tile_ok(int t) { return t == kTile || t == kOsTile9 || t == kOsTile10; }
+inline int64_t onesweep_tiles_of(int64_t m, int t) { return os_tiles(m, t); }
+// A pass of t-record tiles before one of tn-record tiles over m records, and
+// the runtime's rule for the large tile of a sort (lsb_ostile.h: a run may
+// cross at most one of the next pass's sub-array boundaries).
+inline bool onesweep_tile_fits(int t, int tn, int64_t m) { return os_tile_fits(t, tn, m); }
+inline bool onesweep_big_applies(int64_t m, int big) { return os_big_applies(m, big, kTile); }
 // sub_hist (zeroed here) of the digit at `shift`; span as for launch_upsweep.
 hipError_t launch_subhist(const Elem* A, int64_t m, int shift, int grid, uint32_t* sub_hist,
                           uint64_t* span, hipStream_t s);
@@ -118,7 +135,9 @@ hipError_t launch_subhist(const Elem* A, int64_t m, int shift, int grid, uint32_
 // plus a look-back over status (onesweep_tiles(m) * 256 u32 granules, zeroed
 // once at allocation; epoch >= 1, new for every launch over the same m, and
 // the first launch after a zeroing odd: a granule's tag is the epoch's
-// parity, so every launch must write every row).  next_shift >= 0: also
+// parity, so every launch must write every row it may read: a launch of more
+// tiles than the one before on that buffer needs status_fill's rows filled
+// first).  next_shift >= 0: also
 // next_hist (zeroed here) = sub_hist of the digit at next_shift over out.
 // tile_ctr: kOnesweepSubs words of scratch; *err |= 1 if a look-back gave up.
 // -DLSB_OS_PROFILE builds: summed s_memtime ticks of k_onesweep's phases
@@ -285,6 +304,10 @@ struct OnesweepExtra {
   // region_mode 2 and a next-counting pass Packed -> Packed, and a last pass
   // Packed -> Elem.
   bool pack_in = false, pack_out = false;
+  // Records per tile of this pass's input and of the next pass's (0: kTile).
+  // kOsTile9 / kOsTile10 only for a packed middle pass (tile) and for the
+  // packed pass before one (next_tile), and only where onesweep_tile_fits.
+  int tile = 0, next_tile = 0;
 };
 // The runtime's choice of OnesweepExtra::halves for a rank, from a digit's
 // sub-array histogram (kOnesweepSubs x 256 counts of m records): 2 when one

@@ -591,7 +591,8 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void k_scatter(const Elem* __re
 // each chunk's bucket offsets.  Here those come from a decoupled look-back
 // and from a histogram the previous pass produced as it wrote:
 //
-//   * The m records are kTile-record tiles, grouped into kSub = 8 contiguous
+//   * The m records are tiles of T records (kTile = 4096; 5120 for a packed
+//     sort's middle passes, below), grouped into kSub = 8 contiguous
 //     sub-arrays: sub-array x = tiles [x*TT/8, (x+1)*TT/8) (floor), so tile
 //     t lies in sub-array (8t + 7) / TT.  Workgroups with the same
 //     blockIdx % 8 share an XCD; that group takes sub-array blockIdx % 8's
@@ -608,7 +609,9 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void k_scatter(const Elem* __re
 //     Every launch writes every tile's row (a context's m never changes), so
 //     a row holds either this launch's value or the previous launch's, whose
 //     parity differs: status needs no reset (zeroed once at allocation; the
-//     first launch has parity 1), and a granule is half the bytes of a
+//     first launch has parity 1; a launch of more tiles than the one before,
+//     i.e. of smaller tiles, first has the rows that launch left alone filled
+//     with the other parity: status_fill, lsb_ostile.h), and a granule is half the bytes of a
 //     {value, tag} word pair (the status traffic was 6 % of the pass's HBM
 //     bytes).  Buckets b, b+1 travel as one 8-byte write-through (sc1) buffer
 //     store, polled with 8-byte sc1 loads (the guide's R2 form: the data is
@@ -618,8 +621,15 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 128) void k_scatter(const Elem* __re
 //     round trip measured fastest (wider windows: +6 % at 2, +11 % at 4),
 //     and the next tile's id is fetched while this one's records are written.
 //   * NEXT: the pass also accumulates the sub-array histogram of the next
-//     digit over its OUTPUT positions (the next pass's sub-arrays), in LDS,
-//     one add per record, flushed with global atomics at the end.
+//     digit over its OUTPUT positions (the next pass's sub-arrays: whole
+//     tiles of the next pass's size TN, which differs from T at the two seams
+//     of a packed sort), in LDS, one add per record, flushed with global
+//     atomics at the end.
+//   * Tile size per instance: the packed middle passes (PIN, POUT, NEXT; 12 B
+//     per staged record) run 8 waves x 10 records, T = 5120, in 77,160 B of
+//     LDS, still 2 workgroups per CU and no scratch: the per-tile chain
+//     (publish, scan, look-back) is paid 20 % less often, -9.4 % per launch
+//     at 2^30.  Every other instance keeps kTile.
 //   * Workgroup shape: the 64 KiB stage holds a CU to 2 workgroups, so the
 //     whole-stage form runs 8 waves x 8 records (kOsBlock = 512; threads
 //     t < 256 own bucket t, the rest only load, rank, stage and write): the
@@ -1012,7 +1022,8 @@ constexpr int kSegWin = LSB_SEG_WIN;
 // Packed records (12 bytes: the key and the value's low word).  A packed
 // output is staged as keys and values apart (48 KiB instead of 64).  The
 // packing first pass (RG = 1, POUT) also reports a value that does not fit.
-template <int BLOCK, int IPT, bool NEXT, bool C16, int HALVES, bool SEG, bool GATHER, int RG, bool PIN, bool POUT>
+template <int BLOCK, int IPT, bool NEXT, bool C16, int HALVES, bool SEG, bool GATHER, int RG, bool PIN, bool POUT,
+          int TN>
 __device__ __forceinline__ void onesweep_body(
     const Elem* __restrict__ in_, Elem* __restrict__ out_, int64_t m, int shift, int next_shift,
     const uint32_t* __restrict__ sub_hist, uint32_t* __restrict__ next_hist,
@@ -1033,8 +1044,15 @@ __device__ __forceinline__ void onesweep_body(
   // Thread t < 256 owns bucket t (counts, scan, look-back, offsets); with
   // BLOCK = 512 the other threads only load, rank, stage and write.
   static_assert(BLOCK % kBuckets == 0, "bucket threads");
-  // Per-wave digit counters -> tile positions (< 4096): 16-bit at 8 waves,
+  // Per-wave digit counters -> tile positions (< T <= 5120): 16-bit at 8 waves,
   // so the counters of two workgroups still fit a CU beside their stages.
+  static_assert(T < 0xFFFF && T % BLOCK == 0, "16-bit tile positions; 0xFFFF is cut's `never`");
+  // A tile larger than kTile (the packed middle passes, kOsTile10): ten
+  // records in flight leave no room for the histogram column (re-read on a
+  // sub-array change, as the split stage does) nor for a register per rank
+  // (two 16-bit ranks share one).
+  constexpr bool kBig = T > kTile;
+  static_assert(!kBig || (PIN && POUT && NEXT && RG == 0), "large tiles: the packed middle passes only");
   using WC = typename std::conditional<(W > 4), uint16_t, uint32_t>::type;
 
   constexpr int HT = T / HALVES;                // staged records per half
@@ -1055,10 +1073,11 @@ __device__ __forceinline__ void onesweep_body(
   const bool bkt = BLOCK == kBuckets || t < kBuckets;  // a bucket thread
   const int w = t >> 6;
   const uint32_t lane = lane_id();
-  // Tiles of this pass's input (TT) and of the next pass's (TTn: its
-  // sub-arrays are what the next digit is counted by); output slots (mcap).
+  // Tiles of this pass's input (TT) and of the next pass's (TTn, of TN
+  // records each: its sub-arrays are what the next digit is counted by);
+  // output slots (mcap).
   const int64_t TT = RG == 2 ? rg.cap / T * kRegions : (m + T - 1) / T;
-  const int64_t TTn = RG == 1 ? rg.cap / T * kRegions : (m + T - 1) / T;
+  const int64_t TTn = RG == 1 ? rg.cap / TN * kRegions : (m + TN - 1) / TN;
   const int64_t mcap = RG == 1 ? region_stride(rg.cap) * kRegions : m;
   uint32_t racc = 0;                     // RG = 1: thread t's count of region (t, cur_sub)
   uint32_t vhi = 0;                      // packing pass: OR of the values' high words
@@ -1077,12 +1096,13 @@ __device__ __forceinline__ void onesweep_body(
   // bucket column of the sub-array histogram.
   // (The split-stage form re-reads the column when it changes sub-array,
   // a few times per launch: its records need the registers.)
-  uint32_t col[HALVES == 1 ? kSub : 1];
+  constexpr bool kCol = HALVES == 1 && !kBig;
+  uint32_t col[kCol ? kSub : 1];
   uint64_t tot = 0;
 #pragma unroll
   for (int x = 0; x < kSub; ++x) {
     const uint32_t v = bkt && RG != 1 ? sub_hist[x * kBuckets + t] : 0u;
-    if (HALVES == 1) col[x] = v;
+    if (kCol) col[x] = v;
     tot += v;
   }
   uint64_t all;
@@ -1181,7 +1201,7 @@ __device__ __forceinline__ void onesweep_body(
         uint64_t pre = 0;
 #pragma unroll
         for (int xx = 0; xx < kSub; ++xx)
-          pre += xx < x ? (HALVES == 1 ? col[xx] : (bkt ? sub_hist[xx * kBuckets + t] : 0u)) : 0u;
+          pre += xx < x ? (kCol ? col[xx] : (bkt ? sub_hist[xx * kBuckets + t] : 0u)) : 0u;
         base = bstart + pre;
       }
       cur_sub = x;
@@ -1270,6 +1290,26 @@ __device__ __forceinline__ void onesweep_body(
           (void)__hip_atomic_load(const_cast<int32_t*>(&gs.desc[pf].n), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
 #endif
+    } else if constexpr (kBig) {
+      // Ten records in flight: all loads through one buffer descriptor over
+      // the tile's valid records, so a load's address is a 32-bit offset
+      // worked out here, per tile (opaque to the compiler: ten 64-bit
+      // addresses, or ten offsets kept in registers from tile to tile, would
+      // not fit beside the records), and a lane past the tile's end reads
+      // zeros: the whole offset goes through the descriptor's range check
+      // (a scalar offset operand would not).
+      typedef uint32_t v3u __attribute__((ext_vector_type(3)));
+      const int64_t tbu = (int64_t)__builtin_amdgcn_readfirstlane(tile) * T;
+      const int nvu = (int)((m - tbu) < T ? (m - tbu) : T);
+      const __amdgpu_buffer_rsrc_t ri = __builtin_amdgcn_make_buffer_rsrc(
+          const_cast<RIn*>(in + tbu), 0, nvu * (int)sizeof(RIn), 0x00020000);
+      uint32_t vb = (uint32_t)wbase * (uint32_t)sizeof(RIn);
+      asm volatile("" : "+v"(vb));
+#pragma unroll
+      for (int i = 0; i < IPT; ++i) {
+        const v3u x = __builtin_amdgcn_raw_buffer_load_b96(ri, vb + (uint32_t)(i * 64 * (int)sizeof(RIn)), 0, 2);
+        e[i] = RIn{x.x, x.y, x.z};
+      }
     } else {
 #pragma unroll
       for (int i = 0; i < IPT; ++i) {
@@ -1323,7 +1363,8 @@ __device__ __forceinline__ void onesweep_body(
     // (per-wave counters), then the tile's counts: publish the aggregate,
     // put the first look-back window in flight, and scan and stage the tile
     // in LDS (neither needs the global offset) while it travels.
-    uint32_t rk[IPT];
+    uint32_t rk[kBig ? (IPT + 1) / 2 : IPT];
+    auto rank_of = [&](int i) -> uint32_t { return kBig ? (rk[i / 2] >> (16 * (i & 1))) & 0xFFFFu : rk[i]; };
 #pragma unroll
     for (int i = 0; i < IPT; ++i) {
       const bool valid = wbase + i * 64 < nvalid;
@@ -1331,7 +1372,9 @@ __device__ __forceinline__ void onesweep_body(
       const uint64_t mt = match_digit8(d, __ballot(valid));
       const uint32_t below = mbcnt(mt);
       const uint32_t pre = wcnt[w][d];
-      rk[i] = pre + below;
+      if (!kBig) rk[i] = pre + below;
+      else if (i & 1) rk[i / 2] |= (pre + below) << 16;
+      else rk[i / 2] = pre + below;
       if (valid && below == 0) wcnt[w][d] = (WC)(pre + (uint32_t)__popcll(mt));
       if (C16) {
         const int li = wbase + i * 64;
@@ -1386,7 +1429,7 @@ __device__ __forceinline__ void onesweep_body(
         if (wbase + i * 64 < nvalid) {
           const uint32_t d = (uint32_t)(rec_key(e[i]) >> shift) & (kBuckets - 1);
           if (POUT) {
-            const uint32_t p = wcnt[w][d] + rk[i];
+            const uint32_t p = wcnt[w][d] + rank_of(i);
             skey[p] = rec_key(e[i]);
             sval[p] = (uint32_t)rec_val(e[i]);
           } else if (HALVES == 1) {
@@ -1451,21 +1494,15 @@ __device__ __forceinline__ void onesweep_body(
     if (NEXT && bkt) {
       // The run [R, R + cnt) lies in next-pass sub-array x0, except from
       // stage position jb on (x1) when it crosses a sub-array boundary (at
-      // most one: a non-empty sub-array holds >= kTile records).
+      // most one: a non-empty sub-array of the next pass holds >= T records,
+      // onesweep_tile_fits; launch_onesweep refuses the launch otherwise).
       uint32_t c = 0xFFFFu;  // jb = 0xFFFF: never
       if (RG == 1) {
         // Region (t, x) lies in the next pass's sub-array t / 32 (its
         // sub-arrays are 256 whole regions): no run crosses one.
         c = 0xFFFFu | ((uint32_t)(t >> 5) << 16) | ((uint32_t)(t >> 5) << 24);
       } else if (cnt > 0) {
-        const int x0 = sub_of_tile(R / T, TTn);
-        const int64_t bnd = x0 + 1 < kSub ? sub_first_tile(x0 + 1, TTn) * T : mcap;
-        if (R + cnt > bnd) {
-          const int x1 = sub_of_tile(bnd / T, TTn);
-          c = (uint32_t)(lstart + (bnd - R)) | ((uint32_t)x0 << 16) | ((uint32_t)x1 << 24);
-        } else {
-          c = 0xFFFFu | ((uint32_t)x0 << 16) | ((uint32_t)x0 << 24);
-        }
+        c = os_run_cut(R, cnt, lstart, TN, TTn, mcap);
       }
       cut[t] = c;
     }
@@ -1616,6 +1653,11 @@ __device__ __forceinline__ void onesweep_body(
         // G records per batch (the SEG instance: LSB_SEG_BATCH at a time, so
         // its walk registers fit beside them).
         constexpr int G = SEG && LSB_SEG_BATCH > 0 && LSB_SEG_BATCH < HT / BLOCK ? LSB_SEG_BATCH : HT / BLOCK;
+        // The large tile: the thread's stage positions are worked out here,
+        // per tile (opaque to the compiler: as ten 64-bit loop invariants
+        // they took 20 registers for the whole launch, and the records spilled).
+        int tq = t;
+        if constexpr (kBig) asm volatile("" : "+v"(tq));
 #pragma unroll
         for (int k0 = 0; k0 < HT / BLOCK; k0 += G) {
           ROut v[G];
@@ -1639,7 +1681,7 @@ __device__ __forceinline__ void onesweep_body(
           }
 #pragma unroll
           for (int k = 0; k < G; ++k) {
-            const int j = (k0 + k) * BLOCK + t;
+            const int j = (k0 + k) * BLOCK + tq;
             if constexpr (SEG) emit(skew_tag, v[k], j, dl[k] + seg_pos(v[k], j, jend), ct[k]);
             else emit(skew_tag, v[k], j, dl[k] + j, ct[k]);
           }
@@ -1704,16 +1746,15 @@ __device__ __forceinline__ void onesweep_body(
 }
 
 template <int BLOCK, int IPT, bool NEXT, bool C16, int HALVES, bool SEG = false, bool GATHER = false, int RG = 0,
-          bool PIN = false, bool POUT = false>
+          bool PIN = false, bool POUT = false, int TN = BLOCK * IPT>
 __global__ __launch_bounds__(BLOCK, (HALVES == 1 ? 2 : 3) * BLOCK / 256) void k_onesweep(
     const Elem* __restrict__ in, Elem* __restrict__ out, int64_t m, int shift, int next_shift,
     const uint32_t* __restrict__ sub_hist, uint32_t* __restrict__ next_hist,
     uint32_t* __restrict__ status, uint32_t* __restrict__ tile_ctr, uint32_t epoch,
     uint32_t* __restrict__ err, uint64_t* __restrict__ totals,
     unsigned long long* __restrict__ count16, SegPass seg, GatherSrc gs, RegionPass rg) {
-  onesweep_body<BLOCK, IPT, NEXT, C16, HALVES, SEG, GATHER, RG, PIN, POUT>(in, out, m, shift, next_shift, sub_hist,
-                                                                           next_hist, status, tile_ctr, epoch, err,
-                                                                           totals, count16, seg, gs, rg);
+  onesweep_body<BLOCK, IPT, NEXT, C16, HALVES, SEG, GATHER, RG, PIN, POUT, TN>(
+      in, out, m, shift, next_shift, sub_hist, next_hist, status, tile_ctr, epoch, err, totals, count16, seg, gs, rg);
 }
 
 // The placement probe's pass (lsb_context.cpp alloc_records): the same code
@@ -1726,7 +1767,7 @@ __global__ __launch_bounds__(kOsBlock, 2 * kOsBlock / 256) void k_onesweep_probe
     uint32_t* __restrict__ status, uint32_t* __restrict__ tile_ctr, uint32_t epoch,
     uint32_t* __restrict__ err, uint64_t* __restrict__ totals,
     unsigned long long* __restrict__ count16, SegPass seg, GatherSrc gs) {
-  onesweep_body<kOsBlock, kOsIpt, true, false, 1, false, false, 0, false, false>(
+  onesweep_body<kOsBlock, kOsIpt, true, false, 1, false, false, 0, false, false, kTile>(
       in, out, m, shift, next_shift, sub_hist, next_hist, status, tile_ctr, epoch, err, totals, count16, seg, gs,
       RegionPass());
 }
@@ -2444,8 +2485,19 @@ hipError_t launch_onesweep(const Elem* in, Elem* out, int64_t m, int shift, int 
   if (rm < 0 || rm > 2 || (rm != 0 && (!extra.region || rp.cap <= 0 || rp.cap % kTile != 0 ||
                                        rp.cap * kRegions < m || !rp.counts)))
     return hipErrorInvalidValue;
+  // Records per tile of this pass and of the next (over kTile: the packed
+  // middle passes only, lsb_kernels.h).  A middle pass is followed by one of
+  // its own tile size or by the last pass (kTile); the pass that reads the
+  // regional layout (kTile) by a middle pass of any size.
+  const int T = extra.tile ? extra.tile : kTile, TN = extra.next_tile ? extra.next_tile : kTile;
+  const bool mid = rm == 0 && extra.pack_in && extra.pack_out && next_shift >= 0;  // a packed middle pass
+  const bool before_mid = extra.pack_out && next_shift >= 0 && (mid || (rm == 2 && extra.pack_in));
+  if (!onesweep_packed_tile_ok(T) || !onesweep_packed_tile_ok(TN) || (T != kTile && !mid) ||
+      (TN != kTile && !before_mid) || (mid && TN != kTile && TN != T) ||
+      (next_shift >= 0 && !onesweep_tile_fits(T, TN, m)))
+    return hipErrorInvalidValue;
   // Tiles of the input: the regional layout's slots for its reading pass.
-  const int64_t TT = rm == 2 ? rp.cap / kTile * kRegions : (m + kTile - 1) / kTile;
+  const int64_t TT = rm == 2 ? rp.cap / kTile * kRegions : (m + T - 1) / T;
   auto* c16 = reinterpret_cast<unsigned long long*>(extra.count16);
   const bool gat = extra.gather != nullptr;
   // The split stage only for the plain and next-digit forms, never gathered
@@ -2495,9 +2547,18 @@ hipError_t launch_onesweep(const Elem* in, Elem* out, int64_t m, int shift, int 
                            m, shift, next_shift, sub_hist, next_hist, st, tile_ctr, epoch, err, nullptr, nullptr,
                            SegPass(), gsrc, rp);
     } else if (next_shift >= 0 && extra.pack_in) {
-      hipLaunchKernelGGL((k_onesweep<kOsBlock, kOsIpt, true, false, 1, false, false, 2, true, true>), gd, bd, 0, s,
-                         in, out, m, shift, next_shift, sub_hist, next_hist, st, tile_ctr, epoch, err, nullptr,
-                         nullptr, SegPass(), gsrc, rp);
+      if (TN == kOsTile10)
+        hipLaunchKernelGGL((k_onesweep<kOsBlock, kOsIpt, true, false, 1, false, false, 2, true, true, kOsTile10>),
+                           gd, bd, 0, s, in, out, m, shift, next_shift, sub_hist, next_hist, st, tile_ctr, epoch, err,
+                           nullptr, nullptr, SegPass(), gsrc, rp);
+      else if (TN == kOsTile9)
+        hipLaunchKernelGGL((k_onesweep<kOsBlock, kOsIpt, true, false, 1, false, false, 2, true, true, kOsTile9>),
+                           gd, bd, 0, s, in, out, m, shift, next_shift, sub_hist, next_hist, st, tile_ctr, epoch, err,
+                           nullptr, nullptr, SegPass(), gsrc, rp);
+      else
+        hipLaunchKernelGGL((k_onesweep<kOsBlock, kOsIpt, true, false, 1, false, false, 2, true, true>), gd, bd, 0, s,
+                           in, out, m, shift, next_shift, sub_hist, next_hist, st, tile_ctr, epoch, err, nullptr,
+                           nullptr, SegPass(), gsrc, rp);
     } else if (next_shift >= 0) {
       hipLaunchKernelGGL((k_onesweep<kOsBlock, kOsIpt, true, false, 1, false, false, 2>), gd, bd, 0, s, in, out,
                          m, shift, next_shift, sub_hist, next_hist, st, tile_ctr, epoch, err, nullptr, nullptr,
@@ -2516,9 +2577,24 @@ hipError_t launch_onesweep(const Elem* in, Elem* out, int64_t m, int shift, int 
     if (next_shift >= 0) {
       e = hipMemsetAsync(next_hist, 0, sizeof(uint32_t) * kSub * kBuckets, s);
       if (e != hipSuccess) return e;
-      hipLaunchKernelGGL((k_onesweep<kOsBlock, kOsIpt, true, false, 1, false, false, 0, true, true>), gd, bd, 0, s,
-                         in, out, m, shift, next_shift, sub_hist, next_hist, st, tile_ctr, epoch, err, nullptr,
-                         nullptr, SegPass(), gsrc, RegionPass());
+      // A middle pass of IPT records per thread; TN: kTile at the seam before
+      // the last pass, else its own size.
+      auto big = [&](auto ipt, auto tn) {
+        hipLaunchKernelGGL(
+            (k_onesweep<kOsBlock, decltype(ipt)::value, true, false, 1, false, false, 0, true, true, decltype(tn)::value>),
+            gd, bd, 0, s, in, out, m, shift, next_shift, sub_hist, next_hist, st, tile_ctr, epoch, err, nullptr,
+            nullptr, SegPass(), gsrc, RegionPass());
+      };
+      using I9 = std::integral_constant<int, 9>;
+      using I10 = std::integral_constant<int, 10>;
+      if (T == kOsTile10 && TN == T) big(I10(), std::integral_constant<int, kOsTile10>());
+      else if (T == kOsTile10) big(I10(), std::integral_constant<int, kTile>());
+      else if (T == kOsTile9 && TN == T) big(I9(), std::integral_constant<int, kOsTile9>());
+      else if (T == kOsTile9) big(I9(), std::integral_constant<int, kTile>());
+      else
+        hipLaunchKernelGGL((k_onesweep<kOsBlock, kOsIpt, true, false, 1, false, false, 0, true, true>), gd, bd, 0, s,
+                           in, out, m, shift, next_shift, sub_hist, next_hist, st, tile_ctr, epoch, err, nullptr,
+                           nullptr, SegPass(), gsrc, RegionPass());
     } else {
       hipLaunchKernelGGL((k_onesweep<kOsBlock, kOsIpt, false, false, 1, false, false, 0, true, false>), gd, bd, 0, s,
                          in, out, m, shift, 0, sub_hist, nullptr, st, tile_ctr, epoch, err, nullptr, nullptr,

@@ -97,6 +97,7 @@ int onesweep_ensure(Rank& r) {
   HIP_TRY(hipMemsetAsync(r.os_status, 0, tiles * lsb::kBuckets * sizeof(uint32_t), r.stream));
   HIP_TRY(hipMemsetAsync(r.os_ctr, 0, 2 * lsb::kOnesweepSubs * sizeof(uint32_t), r.stream));
   r.os_epoch = 0;
+  r.os_rows = (int64_t)tiles;
   r.os_grid = max_chunks_for_device(r.dev);
   if (r.rg_cap > 0) {  // the regional first pass's buffers (region_ensure)
     const size_t rows = (size_t)lsb::onesweep_tiles(r.rg_cap * lsb::kRegions) * lsb::kBuckets;
@@ -119,7 +120,9 @@ int onesweep_ensure(Rank& r) {
 // launch zeroes them first and restarts the epochs (the first is odd).
 // The pass that reads the regional layout (region_mode 2) has more tiles
 // than the others and keeps its rows on a track of its own (os_status2,
-// os_epoch2).
+// os_epoch2).  A packed sort's middle passes have fewer (larger tiles) and
+// share os_status: a launch of more tiles than the one before first fills
+// the rows that launch left alone (lsb::status_fill; os_rows).
 void zero_status(Rank& r) {
   (void)hipMemsetAsync(r.os_status, 0, (size_t)lsb::onesweep_tiles(r.here) * lsb::kBuckets * sizeof(uint32_t),
                        r.stream);
@@ -129,6 +132,7 @@ void zero_status(Rank& r) {
                          r.stream);
   r.os_epoch = 0;
   r.os_epoch2 = 0;
+  r.os_rows = lsb::onesweep_tiles(r.here);  // every row of epoch 0's parity
 }
 
 int onesweep_launch(lsb_ctx* c, Rank& r, int shift, int next, const uint32_t* hist,
@@ -149,10 +153,19 @@ int onesweep_launch(lsb_ctx* c, Rank& r, int shift, int next, const uint32_t* hi
     r.os_dirty = true;
     return fail(LSB_ERR_HIP, "launch_onesweep", "injected launch failure (LSB_OPT_FAIL_ONESWEEP)");
   }
+  const int64_t rows = lsb::onesweep_tiles_of(r.here, x.tile ? x.tile : lsb::kTile);
   {
     Timer t(c, &r, LSB_K_SCATTER);
-    e = lsb::launch_onesweep(r.A, r.B, r.here, shift, next, hist, next_hist, status, r.os_ctr,
-                             epoch, r.os_ctr + lsb::kOnesweepSubs, r.os_grid, r.stream, x);
+    e = hipSuccess;
+    if (!track2) {
+      const lsb::StatusFill f = lsb::status_fill(r.os_rows, rows, epoch);
+      if (f.count > 0)
+        e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(status + f.first * lsb::kBuckets), (int)f.word,
+                              (size_t)f.count * lsb::kBuckets, r.stream);
+    }
+    if (e == hipSuccess)
+      e = lsb::launch_onesweep(r.A, r.B, r.here, shift, next, hist, next_hist, status, r.os_ctr,
+                               epoch, r.os_ctr + lsb::kOnesweepSubs, r.os_grid, r.stream, x);
   }
   if (e != hipSuccess) {
     (void)hipGetLastError();
@@ -160,6 +173,7 @@ int onesweep_launch(lsb_ctx* c, Rank& r, int shift, int next, const uint32_t* hi
     return fail(LSB_ERR_HIP, "launch_onesweep", hipGetErrorString(e));
   }
   last_epoch = epoch;
+  if (!track2) r.os_rows = rows;
   count_pass_elems(c, r.here);
   std::swap(r.A, r.B);
   return LSB_OK;
@@ -218,6 +232,12 @@ std::vector<int> varying_bytes(uint64_t varying) {
 int onesweep_digits(lsb_ctx* c, Rank& r, const std::vector<int>& digits, int* passes, size_t from = 0,
                     const lsb::RegionPass* rp = nullptr, bool* disarm = nullptr, bool packed = false) {
   uint32_t* hist[2] = {r.os_hist, r.os_hist + lsb::kOnesweepSubs * lsb::kBuckets};
+  // A packed sort's middle passes (Packed -> Packed, after the pass that
+  // reads the regional layout and before the last) take the context's large
+  // tile where it fits (lsb::onesweep_big_applies); the pass before one
+  // counts the next digit by that size.
+  const int big = packed && lsb::onesweep_big_applies(r.here, c->packed_tile) ? c->packed_tile : 0;
+  auto middle = [&](size_t i) { return packed && i > from && i + 1 < digits.size(); };
   for (size_t i = from; i < digits.size(); ++i) {
     const int shift = digits[i] * lsb::kDigitBits;
     const int next = i + 1 < digits.size() ? digits[i + 1] * lsb::kDigitBits : -1;
@@ -230,6 +250,8 @@ int onesweep_digits(lsb_ctx* c, Rank& r, const std::vector<int>& digits, int* pa
     }
     x.pack_in = packed;
     x.pack_out = packed && next >= 0;
+    x.tile = middle(i) ? big : 0;
+    x.next_tile = middle(i + 1) ? big : 0;
     const int rc = onesweep_launch(c, r, shift, next, hist[i & 1], hist[(i + 1) & 1], x);
     if (rc != LSB_OK) {
       if (packed && i > from) {
@@ -245,6 +267,7 @@ int onesweep_digits(lsb_ctx* c, Rank& r, const std::vector<int>& digits, int* pa
       return rc;
     }
     ++*passes;
+    if (middle(i)) c->last_packed_tile = big ? big : lsb::kTile;
     if (disarm) *disarm = false;
   }
   return LSB_OK;

@@ -98,6 +98,7 @@ struct Rank {
   uint32_t* os_hist_h = nullptr;        // pinned mirror of a sub-array histogram
   int os_halves = 1;                    // this sort's k_onesweep stage split (1 or 2)
   uint32_t os_epoch = 0;                // last look-back epoch
+  int64_t os_rows = 0;                  // os_status rows the last launch wrote (lsb::status_fill)
   bool os_dirty = false;                // a launch failed: zero os_status before the next
   int64_t* seg_base = nullptr;          // [kOnesweepSubs][256] the hybrid's bucket bases (k_segfix)
   int os_grid = 0;                      // persistent grid (2 workgroups per CU)
@@ -200,6 +201,7 @@ struct lsb_ctx {
   int os_split = 0;           // LSB_OPT_ONESWEEP_SPLIT: 0 auto, 1 never, 2 always
   int fail_onesweep = 0;      // LSB_OPT_FAIL_ONESWEEP: the n-th k_onesweep launch fails (tests)
   int pack_values = 1;        // LSB_OPT_PACK_VALUES: 0 never, 1 when the values fit 32 bits, 2 always try
+  int packed_tile = lsb::kOsTile10;  // LSB_PACKED_TILE: records per tile of a packed sort's middle passes
   bool pack_wide = false;     // a packing first pass of this context met a value over 32 bits
   bool broken = false;        // a failed packed sort could not restore whole records: no more sorts
   int hybrid = 0;             // LSB_OPT_HYBRID: 0 off, 1 k byte passes (the last one
@@ -211,6 +213,7 @@ struct lsb_ctx {
   uint64_t last_varying = 0;
   int last_first = 0;  // the first pass's form (lsb_get_first_pass)
   int last_records = 0;  // the records between the passes (lsb_get_last_records)
+  int last_packed_tile = 0;  // records per tile of the packed middle passes (lsb_get_last_packed_tile)
   // The plan of the last lsb_count_runs (lsb_plan_runs over every rank's
   // summary), valid until an entry point that can change A (runs_invalidate).
   bool runs_valid = false;

@@ -185,6 +185,7 @@ def _lib() -> ctypes.CDLL:
             "lsb_get_last_sort": (i32, [vp, vp, vp, vp]),
             "lsb_get_first_pass": (i32, [vp, vp]),
             "lsb_get_last_records": (i32, [vp, vp]),
+            "lsb_get_last_packed_tile": (i32, [vp, vp]),
             "lsb_local_ranks": (i32, [vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
             "lsb_generate": (i32, [vp]),
             "lsb_generate_ex": (i32, [vp, i32, ctypes.c_double]),
@@ -232,6 +233,10 @@ def _lib() -> ctypes.CDLL:
             "lsb_strerror": (cp, [i32]),
         }
         for name, (res, args) in sig.items():
+            # An older build given through LSB_LIBRARY (A/B timing against the
+            # parent commit) lacks the newest getter; calling it there raises.
+            if name == "lsb_get_last_packed_tile" and not hasattr(L, name):
+                continue
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -1081,6 +1086,13 @@ class World:
         RECORDS_PACKED_REDONE."""
         f = ctypes.c_int()
         _check(_lib().lsb_get_last_records(self._h, ctypes.byref(f)), "lsb_get_last_records")
+        return int(f.value)
+
+    def last_packed_tile(self) -> int:
+        """Records per tile of the last my_sort's packed middle passes
+        (lsb_get_last_packed_tile; LSB_PACKED_TILE): 0 when none ran."""
+        f = ctypes.c_int()
+        _check(_lib().lsb_get_last_packed_tile(self._h, ctypes.byref(f)), "lsb_get_last_packed_tile")
         return int(f.value)
 
     def kernel_stats(self) -> dict:

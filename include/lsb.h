@@ -646,6 +646,12 @@ int  lsb_get_first_pass(lsb_ctx_t* ctx, int* form);
 #define LSB_RECORDS_PACKED        1
 #define LSB_RECORDS_PACKED_REDONE 2
 int  lsb_get_last_records(lsb_ctx_t* ctx, int* form);
+/* Records per tile of the last lsb_sort's packed middle passes (12-byte
+ * records in and out, LSB_RECORDS_PACKED): 5120 where every sub-array of the
+ * next pass holds at least a tile (from 61441 records on), else 4096; the
+ * environment's LSB_PACKED_TILE = 4096 | 4608 | 5120, read when the context
+ * is created, sets the size asked for.  0 when no such pass ran. */
+int  lsb_get_last_packed_tile(lsb_ctx_t* ctx, int* records);
 /* == globalShuffle(A, B, digit): one pass, result in A. */
 int  lsb_pass(lsb_ctx_t* ctx, int digit);
 int  lsb_sync(lsb_ctx_t* ctx);

@@ -24,6 +24,12 @@
 //   - the planner of the select (lsb_plan_select) for every k of random
 //     partitions against the stable sort of the whole array; its refusals;
 //     lsb_select / lsb_store_select with a null context and bad arguments;
+//   - k_onesweep's tile geometry where passes of different tile sizes meet
+//     (csrc/lsb_ostile.h): the look-back rows' fill decision replayed over
+//     random launch sequences (no launch can read a row of its own parity
+//     that it did not write), the bound under which a large tile applies
+//     against a search over every sub-array, and a run's cut against the
+//     sub-array of each of its slots, for every pair of tile sizes;
 //   - lsb_create / lsb_create_rank_ops with no usable device: the failure
 //     path tears down a half-built context (no leak, no double free).
 #include <algorithm>
@@ -34,6 +40,7 @@
 
 #include "lsb.h"
 #include "lsb_keyform.h"
+#include "lsb_ostile.h"
 #include "lsb_xgeom.h"
 
 static int fails = 0;
@@ -567,6 +574,130 @@ static void select_cases(std::mt19937_64& rng) {
 static int noop_ag(void*, const void*, void*, size_t) { return 0; }
 static int noop_a2a(void*, const void*, const size_t*, const size_t*, void*, const size_t*,
                     const size_t*) { return 0; }
+// ---- k_onesweep's tile geometry (csrc/lsb_ostile.h) ------------------------
+// Sub-array of tile t by the definition: the x with first(x) <= t < first(x + 1).
+static int sub_by_definition(int64_t t, int64_t TT) {
+  for (int x = 0; x < lsb::kOnesweepSubs; ++x)
+    if (lsb::os_sub_first_tile(x, TT) <= t && t < lsb::os_sub_first_tile(x + 1, TT)) return x;
+  return -1;
+}
+
+// Replays launches of `tiles[i]` rows on one row buffer as the runtime queues
+// them (onesweep_launch): the epoch counts up (wrapping to 2 before 2^30),
+// a reset zeroes every row and restarts it.  Returns the rows a launch could
+// have taken for its own without having written them.
+static int64_t replay_rows(const std::vector<int64_t>& tiles, const std::vector<bool>& reset, int64_t cap,
+                           uint32_t epoch0, bool fill) {
+  std::vector<uint8_t> parity((size_t)cap, 0);
+  uint32_t last = epoch0;
+  int64_t prev = cap, bad = 0;
+  if (epoch0 != 0)  // a buffer in use: every row written at epoch0
+    for (auto& p : parity) p = epoch0 & 1u;
+  for (size_t i = 0; i < tiles.size(); ++i) {
+    if (reset[i]) {
+      std::fill(parity.begin(), parity.end(), 0);
+      last = 0;
+      prev = cap;
+    }
+    uint32_t epoch = last + 1;
+    if (epoch >= (1u << 30)) epoch = 2;
+    const lsb::StatusFill f = lsb::status_fill(prev, tiles[i], epoch);
+    CHECK(f.count >= 0 && f.first >= 0 && f.first + f.count <= cap, "fill inside the buffer");
+    CHECK(f.count == 0 || (f.first == prev && f.first + f.count == tiles[i]), "fill = the rows the last launch left");
+    CHECK((f.word & 0x7FFFFFFFu) == 0, "fill word: a parity and nothing else");
+    if (fill)
+      for (int64_t r = f.first; r < f.first + f.count; ++r) parity[(size_t)r] = (uint8_t)(f.word >> 31);
+    for (int64_t r = 0; r < tiles[i]; ++r) bad += parity[(size_t)r] == (epoch & 1u) ? 1 : 0;
+    for (int64_t r = 0; r < tiles[i]; ++r) parity[(size_t)r] = epoch & 1u;
+    prev = tiles[i];
+    last = epoch;
+  }
+  return bad;
+}
+
+static void onesweep_tile_cases(std::mt19937_64& rng) {
+  const int sizes[] = {4096, 4608, 5120};
+  // The rows' fill: random tile counts, resets and starting epochs.
+  int64_t unfilled = 0;
+  for (int rep = 0; rep < 200; ++rep) {
+    const int64_t cap = 1 + (int64_t)(rng() % 300);
+    const size_t len = 1 + rng() % 40;
+    std::vector<int64_t> tiles(len);
+    std::vector<bool> reset(len);
+    for (size_t i = 0; i < len; ++i) {
+      // mostly the two counts of a sort (cap and 4 / 5 of it), sometimes any
+      const uint64_t k = rng() % 4;
+      tiles[i] = k == 0 ? cap : k == 1 ? (cap * 4 + 4) / 5 : 1 + (int64_t)(rng() % (uint64_t)cap);
+      reset[i] = rng() % 16 == 0;
+    }
+    const uint32_t epoch0 = rep % 3 == 0 ? 0u : rep % 3 == 1 ? (uint32_t)(rng() % 1000) : (1u << 30) - 1u - (uint32_t)(rng() % 8);
+    CHECK(replay_rows(tiles, reset, cap, epoch0, true) == 0, "a launch takes only rows it wrote");
+    unfilled += replay_rows(tiles, reset, cap, epoch0, false);
+  }
+  CHECK(unfilled > 0, "without the fill the replay finds stale rows (the check has teeth)");
+  // The sort's own sequence at 2^30 records: pass 0 (4096), passes 2-6 (5120), pass 7 (4096), twice.
+  {
+    const int64_t t4 = lsb::os_tiles(int64_t(1) << 30, 4096), t5 = lsb::os_tiles(int64_t(1) << 30, 5120);
+    const std::vector<int64_t> seq = {t4, t5, t5, t5, t5, t5, t4, t4, t5, t5, t5, t5, t5, t4};
+    CHECK(replay_rows(seq, std::vector<bool>(seq.size(), false), t4, 0, true) == 0, "two packed sorts");
+    CHECK(replay_rows(seq, std::vector<bool>(seq.size(), false), t4, 0, false) > 0, "two packed sorts, no fill");
+    const lsb::StatusFill f = lsb::status_fill(t5, t4, 7);
+    CHECK(f.first == t5 && f.count == t4 - t5 && f.word == 0u, "odd epoch: even fill");
+    CHECK(lsb::status_fill(t5, t4, 8).word == 0x80000000u, "even epoch: odd fill, not zero");
+    CHECK(lsb::status_fill(t4, t5, 8).count == 0 && lsb::status_fill(t4, t4, 8).count == 0, "no fill for fewer rows");
+  }
+  // The applicability bound against a search: os_tile_fits must rule out
+  // every m at which a run of t records could cover a whole non-empty
+  // sub-array of the next pass and go on past it.
+  std::vector<int64_t> ms;
+  for (int64_t m = 1; m <= 20 * 5120; m += 509) ms.push_back(m);
+  for (int64_t m : {int64_t(61440), int64_t(61441), int64_t(65536), int64_t(81920), int64_t(81921), int64_t(300007),
+                    (int64_t(1) << 20) + 12345, int64_t(1) << 30})
+    ms.push_back(m);
+  for (int64_t m : ms)
+    for (int t : sizes)
+      for (int tn : sizes) {
+        const int64_t TTn = lsb::os_tiles(m, tn);
+        bool two = false;  // two boundaries within t - 2 slots of each other, records on both sides
+        int64_t prevb = -1;
+        for (int x = 1; x < lsb::kOnesweepSubs; ++x) {
+          const int64_t b = lsb::os_sub_first_tile(x, TTn) * tn;
+          if (b <= 0 || b >= m || b == prevb) continue;
+          if (prevb >= 0 && b - prevb <= t - 2) two = true;
+          prevb = b;
+        }
+        if (lsb::os_tile_fits(t, tn, m)) CHECK(!two, "a fitting tile's run crosses at most one boundary");
+        if (t <= tn) CHECK(lsb::os_tile_fits(t, tn, m), "a tile no larger than the next pass's always fits");
+      }
+  CHECK(!lsb::os_big_applies(61440, 5120, 4096) && lsb::os_big_applies(61441, 5120, 4096), "5120 from 16 tiles of 4096 on");
+  CHECK(lsb::os_big_applies(65536, 5120, 4096) && lsb::os_big_applies(65536, 4608, 4096), "the smallest regional sort");
+  CHECK(!lsb::os_big_applies(int64_t(1) << 30, 4096, 4096), "4096 is not a large tile");
+  // A run's cut against the sub-array of each of its slots, both tile sizes.
+  for (int rep = 0; rep < 4000; ++rep) {
+    const int t = sizes[rng() % 3], tn = sizes[rng() % 3];
+    const int64_t m = rep % 4 == 0 ? 61441 + (int64_t)(rng() % 30000) : 1 + (int64_t)(rng() % 2000000);
+    if (!lsb::os_tile_fits(t, tn, m)) continue;
+    const int64_t TTn = lsb::os_tiles(m, tn);
+    // runs near a boundary half of the time
+    int64_t R = (int64_t)(rng() % (uint64_t)m);
+    if (rep % 2 == 0) {
+      const int64_t b = lsb::os_sub_first_tile(1 + (int)(rng() % 7), TTn) * tn;
+      R = std::max<int64_t>(0, std::min<int64_t>(m - 1, b - (int64_t)(rng() % (uint64_t)t)));
+    }
+    const uint32_t cnt = (uint32_t)std::min<int64_t>(m - R, 1 + (int64_t)(rng() % (uint64_t)t));
+    const uint32_t lstart = (uint32_t)(rng() % (uint64_t)(t - cnt + 1));
+    const uint32_t c = lsb::os_run_cut(R, cnt, lstart, tn, TTn, m);
+    bool ok = true;
+    for (uint32_t p = 0; p < cnt; ++p) {
+      const uint32_t j = lstart + p;
+      const int xs = j >= (c & 0xFFFFu) ? (int)(c >> 24) : (int)((c >> 16) & 0xFFu);
+      const int64_t tile = (R + p) / tn;
+      ok = ok && xs == sub_by_definition(tile, TTn) && xs == lsb::os_sub_of_tile(tile, TTn);
+    }
+    CHECK(ok, "every slot of a run counted in the sub-array that holds it");
+  }
+}
+
 static int noop_min(void*, int64_t*) { return 0; }
 static int noop_bar(void*) { return 0; }
 
@@ -602,6 +733,7 @@ int main() {
   keyform_case(rng);
   runs_cases(rng);
   select_cases(rng);
+  onesweep_tile_cases(rng);
   uint64_t col[4] = {0, 1, 2, 3};  // host memory: never reaches a device call with a null context
   CHECK(lsb_load_columns(nullptr, 0, 0, 4, col, LSB_KEY_U64, col, 8, 0) == LSB_ERR_INVALID, "load: null ctx");
   CHECK(lsb_store_columns(nullptr, 0, 0, 4, col, LSB_KEY_U64, col, 8, 0) == LSB_ERR_INVALID, "store: null ctx");
