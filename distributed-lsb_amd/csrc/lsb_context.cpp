@@ -177,6 +177,7 @@ void free_rank(Rank& r, const lsb_ctx* c) {
   (void)hipFree(r.run_sum);
   (void)hipFree(r.run_lead);
   (void)hipFree(r.run_part);
+  (void)hipFree(r.scan_buf);
   (void)hipFree(r.sel_buf);
   (void)hipFree(r.sel_gather);
   (void)hipFree(r.sel_cnt);

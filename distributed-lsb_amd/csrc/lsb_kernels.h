@@ -547,6 +547,45 @@ constexpr int kLabelKeep = 0, kLabelByValue = 1;  // == LSB_LABEL_*
 hipError_t launch_run_label(const Elem* A, Elem* B, int64_t here, int64_t gid0, int head0, const uint32_t* tile_cnt,
                             const int64_t* tile_base, int mode, uint32_t* err, hipStream_t s);
 
+// The scan within the runs (lsb_plan_scan / lsb_store_scan / lsb_scan_runs,
+// include/lsb.h): per record, op over the values of its run's
+// records up to and including it.  Ops 0..2 are the reductions' (the same four
+// combines); kScanCount and kScanStart take every record's operand as 1 under
+// the integer add, so the inclusive scan c of a record gives its position in
+// its run, c - 1, and its run's first global position, its own - (c - 1).
+constexpr int kScanCount = 3, kScanStart = 4;  // == LSB_SCAN_COUNT, LSB_SCAN_START
+inline bool scan_valid(int op, int val_type) {
+  return reduce_valid(op, val_type) || ((op == kScanCount || op == kScanStart) && val_type == kKeyU64);
+}
+inline int scan_form(int op, int val_type) { return op >= kScanCount ? kRedAdd : red_form(op, val_type); }
+// One more read of A after launch_run_count (here > 0), then one workgroup.
+// tile_open[t] = the combine over tile t's records from its last head on (the
+// whole tile without one; position 0 is a head exactly when head0);
+// tile_in[t] = the combine, in tile order, over the tile_open of the tiles
+// before t back to and including the last one with a head (the identity for
+// tile 0): what the rank's earlier tiles add to the run open at t's first
+// record.  Both in the combine's working form, run_tiles(here) words each.
+// *trail = the same over all the rank's tiles, in the caller's bits: the
+// combine over the rank's records from its last head on.  A tile whose heads
+// are not the tile_cnt[t] of the count sets *err.
+hipError_t launch_run_scan_plan(const Elem* A, int64_t here, int head0, const uint32_t* tile_cnt, int op,
+                                int val_type, uint64_t* tile_open, uint64_t* tile_in, uint64_t* trail,
+                                uint32_t* err, hipStream_t s);
+// One more read of A and one write.  The result of the record at slot i is
+// ((carry + tile_in[t]) + the scan inside tile t) for i < lead, (tile_in[t] +
+// the scan inside t) for a later record in front of its tile's first head,
+// and the scan inside t otherwise; carry in the caller's bits, lead = the
+// rank's first head (0 when head0, `here` without one).  gbase = the global
+// position of slot 0 (kScanStart).  sink: kScanColumn writes out[i] = the
+// result (8-byte elements), kScanKeep out[i] = {A[i].key, result} and
+// kScanByValue {A[i].val, result} (16-byte records, another buffer than A).
+// A tile whose heads are not the tile_cnt[t] of the count sets *err and writes
+// nothing; no index leaves [0, here).
+constexpr int kScanColumn = 0, kScanKeep = 1, kScanByValue = 2;
+hipError_t launch_run_scan_write(const Elem* A, int64_t here, int64_t gbase, int head0, int64_t lead,
+                                 const uint32_t* tile_cnt, const uint64_t* tile_in, int op, int val_type,
+                                 uint64_t carry, int sink, void* out, uint32_t* err, hipStream_t s);
+
 // The k-th key and the first k + 1 records without a sort (lsb_select.hip;
 // lsb_select / lsb_store_select, include/lsb.h).
 // A rank's table of a round: kSelHist counts, then two words (round one: the

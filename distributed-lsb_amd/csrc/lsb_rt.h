@@ -162,6 +162,7 @@ struct Rank {
   uint64_t* run_sum = nullptr;          // [kRunSumWords] summary words, k_run_write's error word
   uint64_t* run_lead = nullptr;         // [run_tiles(here)] k_run_reduce's tile leads (lsb_plan_reduce)
   uint64_t* run_part = nullptr;         // [kRunLeadParts + 1] k_run_lead's partials, then the leading run's word
+  uint64_t* scan_buf = nullptr;         // [2 run_tiles(here) + 2] tile_open, tile_in, the trail word, the scan's error word (lsb_plan_scan)
   // The select (lsb_select.cpp), allocated on first use.
   uint64_t* sel_buf = nullptr;          // [kSelBufWords] a round's table, then lsb_store_select's error word
   uint64_t* sel_gather = nullptr;       // [P][kSelWords] all-gathered tables (one rank per process)
@@ -226,6 +227,11 @@ struct lsb_ctx {
   bool reduce_valid = false;
   int reduce_op = 0, reduce_type = 0;
   std::vector<uint64_t> run_tail;                     // [P]
+  // The plan of the last lsb_plan_scan (lsb_plan_run_carries over every
+  // rank's trailing word), beside the reduce plan; it dies with the run plan.
+  bool scan_valid = false;
+  int scan_op = 0, scan_type = 0;
+  std::vector<uint64_t> run_carry;                    // [P]
   // The plan of the last lsb_select (lsb_plan_select over every rank's
   // counts), valid until an entry point that can change A (select_invalidate);
   // the run plan and this one do not end each other.  What that call ran
@@ -383,7 +389,7 @@ Rank* local_rank(lsb_ctx* c, int rank);
 int check_ctx(const lsb_ctx* c);
 // A is about to change: lsb_store_runs and lsb_label_runs need a new
 // lsb_count_runs, lsb_store_reduce a new lsb_plan_reduce after it.
-inline void runs_invalidate(lsb_ctx* c) { c->runs_valid = c->reduce_valid = false; }
+inline void runs_invalidate(lsb_ctx* c) { c->runs_valid = c->reduce_valid = c->scan_valid = false; }
 // A is about to change: lsb_store_select needs a new lsb_select.
 inline void select_invalidate(lsb_ctx* c) { c->select_valid = false; }
 // A caller's column of cnt elements of `elem` bytes at p, before a kernel may

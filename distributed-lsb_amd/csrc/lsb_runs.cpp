@@ -2,7 +2,9 @@
 // the ranks' summary words, the collective count and the local store; and the
 // reductions over the runs' values (§7.3): the host planner over the ranks'
 // leading runs, the collective plan and the local store; and the run id of
-// every record (§7.4): one local call over the run plan.
+// every record (§7.4): one local call over the run plan; and the scan within
+// the runs (§7.6): the host planner over the ranks' trailing runs, the
+// collective plan, the local store and the records form.
 #include "lsb_keyform.h"
 #include "lsb_rt.h"
 
@@ -42,6 +44,84 @@ int ensure_run_scratch(Rank& r) {
 int ensure_reduce_scratch(Rank& r) {
   if (!r.run_lead) LSB_TRY(dev_alloc(&r.run_lead, (size_t)lsb::run_tiles(r.here)));
   if (!r.run_part) LSB_TRY(dev_alloc(&r.run_part, (size_t)lsb::kRunLeadParts + 1));
+  return LSB_OK;
+}
+
+// The scan's scratch (lsb_plan_scan), freed with the run scratch: tile_open
+// and tile_in, then the rank's trail word and the scan's own error word.
+int ensure_scan_scratch(Rank& r) {
+  if (!r.scan_buf) LSB_TRY(dev_alloc(&r.scan_buf, 2 * (size_t)lsb::run_tiles(r.here) + 2));
+  return LSB_OK;
+}
+uint64_t* scan_open(const Rank& r) { return r.scan_buf; }
+uint64_t* scan_in(const Rank& r) { return r.scan_buf + lsb::run_tiles(r.here); }
+uint64_t* scan_trail(const Rank& r) { return r.scan_buf + 2 * lsb::run_tiles(r.here); }
+uint32_t* scan_err(const Rank& r) { return reinterpret_cast<uint32_t*>(scan_trail(r) + 1); }
+
+// Every rank's trail word on the host, the way gather_leads moves the leads;
+// empty ranks give zeros.
+int gather_trails(lsb_ctx* c, std::vector<uint64_t>& trail) {
+  const int P = c->P;
+  trail.assign((size_t)P, 0);
+  if (c->mode == Mode::kLoopback) {
+    for (Rank& r : c->ranks) {
+      if (r.here == 0) continue;
+      HIP_TRY(hipSetDevice(r.dev));
+      HIP_TRY(hipStreamSynchronize(r.stream));
+      HIP_TRY(hipMemcpy(&trail[(size_t)r.rank], scan_trail(r), 8, hipMemcpyDeviceToHost));
+    }
+    return LSB_OK;
+  }
+  Rank& r = c->ranks[0];
+  HIP_TRY(hipSetDevice(r.dev));
+  uint64_t* d = r.gather;  // >= P entries
+  HIP_TRY(hipMemsetAsync(d, 0, sizeof(uint64_t) * P, r.stream));
+  if (r.here > 0) HIP_TRY(hipMemcpyAsync(d + r.rank, scan_trail(r), 8, hipMemcpyDeviceToDevice, r.stream));
+  LSB_TRY(coll_allgather_u64(c, r, d + r.rank, d, 1));
+  HIP_TRY(hipMemcpyAsync(trail.data(), d, sizeof(uint64_t) * P, hipMemcpyDeviceToHost, r.stream));
+  HIP_TRY(hipStreamSynchronize(r.stream));
+  return LSB_OK;
+}
+
+// The OR of the local ranks' scan error words, after their streams are done.
+int scan_errors(lsb_ctx* c, uint32_t* any) {
+  *any = 0;
+  for (Rank& r : c->ranks) {
+    if (r.here == 0) continue;
+    HIP_TRY(hipSetDevice(r.dev));
+    uint32_t h = 0;
+    HIP_TRY(hipMemcpyAsync(&h, scan_err(r), sizeof h, hipMemcpyDeviceToHost, r.stream));
+    HIP_TRY(hipStreamSynchronize(r.stream));
+    *any |= h;
+  }
+  return LSB_OK;
+}
+
+// The write kernel of rank r into out, with the plan's carry and the rank's
+// first head from the run plan's summary.
+hipError_t launch_scan_write(lsb_ctx* c, Rank& r, int sink, void* out) {
+  const int head0 = c->run_head0[r.rank];
+  const int64_t lead = head0 ? 0 : (int64_t)c->run_words[(size_t)r.rank * 4 + kLead];
+  return lsb::launch_run_scan_write(r.A, r.here, (int64_t)r.rank * c->per, head0, lead, r.run_cnt, scan_in(r),
+                                    c->scan_op, c->scan_type, c->run_carry[r.rank], sink, out, scan_err(r),
+                                    r.stream);
+}
+
+// lsb_scan_runs' work, as label_ranks: every non-empty local rank's A -> B on
+// its own stream, then every rank's error word; the ranks swap only when none
+// of them found A changed.
+int scan_ranks(lsb_ctx* c, int mode) {
+  for (Rank& r : c->ranks) {
+    if (r.here == 0) continue;
+    HIP_TRY(hipSetDevice(r.dev));
+    HIP_TRY(hipMemsetAsync(scan_err(r), 0, sizeof(uint64_t), r.stream));
+    HIP_TRY(launch_scan_write(c, r, mode == LSB_LABEL_KEEP ? lsb::kScanKeep : lsb::kScanByValue, r.B));
+  }
+  uint32_t any = 0;
+  LSB_TRY(scan_errors(c, &any));
+  if (any) return fail(LSB_ERR_STATE, "lsb_scan_runs", "A changed since lsb_count_runs: no rank was written");
+  for (Rank& r : c->ranks)
+    if (r.here > 0) std::swap(r.A, r.B);
   return LSB_OK;
 }
 
@@ -360,6 +440,120 @@ int lsb_store_reduce(lsb_ctx_t* c, int rank, int64_t cap, void* out_dev, int64_t
     return fail(LSB_ERR_STATE, where, "A changed since lsb_count_runs: the outputs are unspecified");
   }
   return LSB_OK;
+}
+
+int lsb_plan_run_carries(int64_t n_total, int num_ranks, const uint64_t* summary, int op, int val_type,
+                         const uint64_t* trail, uint64_t* carry) {
+  const char* where = "lsb_plan_run_carries";
+  if (n_total < 0 || num_ranks < 1 || num_ranks > LSB_MAX_RANKS || !summary || !trail || !carry ||
+      !lsb::scan_valid(op, val_type))
+    return fail(LSB_ERR_INVALID, where, "arguments");
+  const int P = num_ranks;
+  LSB_TRY(check_summary(n_total, P, summary, where));
+  const int F = lsb::scan_form(op, val_type);
+  const lsb::KeyForm form = lsb::key_form(val_type, 0);
+  // own[s]: rank s has a head of its own (an inner one, or a run starts at its slot 0: lsb_plan_runs' head0).
+  bool own[LSB_MAX_RANKS] = {};
+  for (int r = 0, prev = -1; r < P; ++r) {
+    if (here_of(n_total, P, r) == 0) continue;
+    const uint64_t* w = summary + (size_t)r * 4;
+    own[r] = w[kInner] > 0 || prev < 0 || summary[(size_t)prev * 4 + kLast] != w[kFirst];
+    prev = r;
+  }
+  for (int r = 0; r < P; ++r) {
+    uint64_t acc = lsb::red_identity(F);
+    if (here_of(n_total, P, r) > 0) {
+      // lsb_plan_run_tails' walk the other way: down from r - 1 through the
+      // ranks whose last run is r's leading run, to the one that holds its head.
+      const uint64_t* w = summary + (size_t)r * 4;
+      int chain[LSB_MAX_RANKS], len = 0;
+      for (int s = r - 1; s >= 0; --s) {
+        if (here_of(n_total, P, s) == 0) continue;
+        if (summary[(size_t)s * 4 + kLast] != w[kFirst]) break;
+        chain[len++] = s;
+        if (own[s]) break;
+      }
+      // the fold is a left one in increasing rank order
+      while (len > 0) acc = lsb::red(F, acc, lsb::red_load(F, trail[chain[--len]], form));
+    }
+    carry[r] = lsb::red_store(F, acc, form);
+  }
+  return LSB_OK;
+}
+
+int lsb_plan_scan(lsb_ctx_t* c, int op, int val_type) {
+  const char* where = "lsb_plan_scan";
+  LSB_TRY(check_ctx(c));
+  if (!lsb::scan_valid(op, val_type)) return fail(LSB_ERR_INVALID, where, "op or value type");
+  if (!c->runs_valid) return fail(LSB_ERR_STATE, where, "no valid plan: call lsb_count_runs after the last change of A");
+  c->scan_valid = false;
+  const int P = c->P;
+  std::vector<uint64_t> trail((size_t)P, 0);
+  if (c->n > 0) {
+    for (Rank& r : c->ranks) {
+      if (r.here == 0) continue;
+      HIP_TRY(hipSetDevice(r.dev));
+      LSB_TRY(ensure_scan_scratch(r));
+      HIP_TRY(hipMemsetAsync(scan_err(r), 0, sizeof(uint64_t), r.stream));
+      HIP_TRY(lsb::launch_run_scan_plan(r.A, r.here, c->run_head0[r.rank], r.run_cnt, op, val_type, scan_open(r),
+                                        scan_in(r), scan_trail(r), scan_err(r), r.stream));
+    }
+    // The gather comes first: a rank whose guard fired still takes part in the collective.
+    LSB_TRY(gather_trails(c, trail));
+    uint32_t any = 0;
+    LSB_TRY(scan_errors(c, &any));
+    if (any) {
+      runs_invalidate(c);
+      return fail(LSB_ERR_STATE, where, "A changed since lsb_count_runs");
+    }
+  }
+  c->run_carry.assign((size_t)P, 0);
+  if (lsb_plan_run_carries(c->n, P, c->run_words.data(), op, val_type, trail.data(), c->run_carry.data()) != LSB_OK)
+    return fail(LSB_ERR_STATE, where, "the run plan's summary is inconsistent");
+  c->scan_op = op;
+  c->scan_type = val_type;
+  c->scan_valid = true;
+  return LSB_OK;
+}
+
+int lsb_store_scan(lsb_ctx_t* c, int rank, int64_t cap, void* out_dev, int64_t* count) {
+  const char* where = "lsb_store_scan";
+  LSB_TRY(check_ctx(c));
+  Rank* r = local_rank(c, rank);
+  if (!r || cap < 0) return fail(LSB_ERR_INVALID, where, "rank or cap");
+  if (!c->runs_valid || !c->scan_valid)
+    return fail(LSB_ERR_STATE, where, "no valid plan: call lsb_count_runs and lsb_plan_scan after the last change of A");
+  const int64_t mine = r->here;
+  if (count) *count = mine;
+  if (cap < mine) return fail(LSB_ERR_INVALID, where, "cap below the rank's records");
+  if (mine == 0) return LSB_OK;  // nothing to write: the pointer is not looked at
+  if (!out_dev) return fail(LSB_ERR_INVALID, where, "null output");
+  HIP_TRY(hipSetDevice(r->dev));
+  LSB_TRY(check_column(*r, out_dev, 8, cap, where));
+  HIP_TRY(hipStreamSynchronize(r->stream));
+  HIP_TRY(hipMemsetAsync(scan_err(*r), 0, sizeof(uint64_t), r->stream));
+  HIP_TRY(launch_scan_write(c, *r, lsb::kScanColumn, out_dev));
+  uint32_t h = 0;
+  HIP_TRY(hipMemcpyAsync(&h, scan_err(*r), sizeof h, hipMemcpyDeviceToHost, r->stream));
+  HIP_TRY(hipStreamSynchronize(r->stream));
+  if (h) {
+    runs_invalidate(c);
+    return fail(LSB_ERR_STATE, where, "A changed since lsb_count_runs: the output is unspecified");
+  }
+  return LSB_OK;
+}
+
+int lsb_scan_runs(lsb_ctx_t* c, int mode) {
+  const char* where = "lsb_scan_runs";
+  LSB_TRY(check_ctx(c));
+  if (mode != LSB_LABEL_KEEP && mode != LSB_LABEL_BY_VALUE) return fail(LSB_ERR_INVALID, where, "mode");
+  if (!c->runs_valid || !c->scan_valid)
+    return fail(LSB_ERR_STATE, where, "no valid plan: call lsb_count_runs and lsb_plan_scan after the last change of A");
+  // The records change (or a rank found them changed already): the plans end here either way.
+  const int rc = c->n > 0 ? scan_ranks(c, mode) : LSB_OK;
+  runs_invalidate(c);
+  select_invalidate(c);
+  return rc;
 }
 
 }  // extern "C"

@@ -17,8 +17,16 @@
 // and the run id of every record (lsb_label_runs):
 //   k_run_label  one more read of A and one write of B: every record with
 //                the global index of its run
+// and the scan within the runs (lsb_plan_scan / lsb_store_scan /
+// lsb_scan_runs):
+//   k_run_scan_tile   one more read of A: what every tile leaves open at its end
+//   k_run_scan_chain  one workgroup: what the tiles before it bring into every
+//                     tile, and the rank's trailing word
+//   k_run_scan_write  one more read of A and one write: every record's result,
+//                     into a column or into the records of B
 // No workgroup waits for another: a tile's base is ready before k_run_write,
-// k_run_reduce or k_run_label starts, every tile's lead before k_run_carry does.  No
+// k_run_reduce or k_run_label starts, every tile's lead before k_run_carry does,
+// every tile_open before k_run_scan_chain, every tile_in before k_run_scan_write.  No
 // floating-point atomics: the order of every addition is the code's.
 // Positions, bases and counts are 64-bit throughout.
 #include "lsb_kernels.h"
@@ -537,6 +545,262 @@ __global__ __launch_bounds__(kRunBlock) void k_run_lead_sum(const uint64_t* __re
   if (threadIdx.x == 0) *out = red_store(F, acc, form);
 }
 
+// ---- the scan within the runs -------------------------------
+// The scan's op as the kernels are instantiated: the four combines, and the
+// two that count (every operand 1 under the integer add).
+enum ScanKind { kSkAdd = kRedAdd, kSkFadd = kRedFadd, kSkMin = kRedMin, kSkMax = kRedMax, kSkCount = 4, kSkStart = 5 };
+constexpr int sk_form(int K) { return K >= kSkCount ? (int)kRedAdd : K; }
+
+// A wave's items after wave_heads, x[j] in the combine's working form:
+// x[j] becomes the segmented inclusive scan in position order from the wave's
+// first record on, within an item across the lanes (wave_seg_scan), between
+// the items by the value of lane 63: k_run_reduce's first loop.  Returns what
+// the wave leaves open at its end (its records since its last head, all of
+// them without one; the same in every lane), *cnt = its heads.
+template <int F>
+__device__ __forceinline__ uint64_t wave_scan_items(const uint64_t (&heads)[kRunItems], uint64_t (&x)[kRunItems],
+                                                    int lane, uint32_t* cnt) {
+  const uint64_t le = ~0ull >> (63 - lane);  // the lanes at or below this one
+  uint64_t carry = red_identity(F);
+  uint32_t c = 0;
+#pragma unroll
+  for (int j = 0; j < kRunItems; ++j) {
+    const uint64_t m = heads[j] & le;
+    // the lanes below this one that belong to its segment
+    const int reach = m ? lane - (63 - __builtin_clzll(m)) : lane;
+    uint64_t v = wave_seg_scan<F>(x[j], lane, reach);
+    if (m == 0) v = red<F>(carry, v);  // in front of the item's first head: the segment open at the item's start
+    carry = last_lane(v);
+    c += (uint32_t)__popcll(heads[j]);
+    x[j] = v;
+  }
+  *cnt = c;
+  return carry;
+}
+
+// The waves' hand-over through LDS (s_part, s_cnt: kRunWaves entries each):
+// every wave leaves its open part and its head count, and folds those of the
+// waves before it in wave order, a wave with a head starting anew.  Returns
+// what they leave open at this wave's first record; *before = their heads;
+// *open = the same fold over all the waves, the tile's records since its last
+// head; *total = the tile's heads.  One barrier inside; the caller puts another
+// before the next tile's call.
+template <int F>
+__device__ __forceinline__ uint64_t tile_hand_over(uint64_t part, uint32_t cnt, int lane, int wave, uint64_t* s_part,
+                                                   uint32_t* s_cnt, uint32_t* before, uint64_t* open,
+                                                   uint32_t* total) {
+  if (lane == 0) {
+    s_part[wave] = part;
+    s_cnt[wave] = cnt;
+  }
+  __syncthreads();
+  uint64_t acc = red_identity(F), cw = acc;
+  uint32_t t = 0, b = 0;
+#pragma unroll
+  for (int w = 0; w < kRunWaves; ++w) {
+    if (w == wave) {
+      cw = acc;
+      b = t;
+    }
+    acc = s_cnt[w] ? s_part[w] : red<F>(acc, s_part[w]);
+    t += s_cnt[w];
+  }
+  *before = b;
+  *open = acc;
+  *total = t;
+  return cw;
+}
+
+// The records' operands in the working form: the value (encoded for min and
+// max), 1 for the counting kinds, the identity past the rank's end, so that
+// the last tile's open part holds the rank's records only.
+template <int K>
+__device__ __forceinline__ void scan_operands(uint64_t (&x)[kRunItems], int64_t wave0, int64_t here, int lane,
+                                              const KeyForm& form) {
+  constexpr int F = sk_form(K);
+#pragma unroll
+  for (int j = 0; j < kRunItems; ++j) {
+    const int64_t i = wave0 + j * 64 + lane;
+    x[j] = i < here ? (K >= kSkCount ? 1ull : red_load(F, x[j], form)) : red_identity(F);
+  }
+}
+
+// tile_open[t] = the combine over tile t's records from its last head on, in
+// the working form (the whole tile without a head; position 0 is a head
+// exactly when head0).  The recount is k_run_reduce's: a tile whose heads are
+// not tile_cnt[t] sets *err.
+template <int K>
+__global__ __launch_bounds__(kRunBlock) void k_run_scan_tile(const Elem* __restrict__ A, int64_t here, int64_t tiles,
+                                                             uint32_t head0, const uint32_t* __restrict__ tile_cnt,
+                                                             int val_type, uint64_t* __restrict__ tile_open,
+                                                             uint32_t* __restrict__ err) {
+  constexpr int F = sk_form(K);
+  __shared__ uint64_t s_part[kRunWaves];
+  __shared__ uint32_t s_cnt[kRunWaves];
+  const int lane = run_lane(), wave = (int)(threadIdx.x >> 6);
+  const KeyForm form = key_form(val_type, 0);
+  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    uint64_t key[kRunItems], x[kRunItems], heads[kRunItems];
+    const int64_t wave0 = tile * kTile + (int64_t)wave * kRunWaveRecs;
+    wave_heads<(K < kSkCount)>(A, here, wave0, head0 != 0, key, x, heads);
+    scan_operands<K>(x, wave0, here, lane, form);
+    uint32_t cnt, before, total;
+    uint64_t open;
+    const uint64_t part = wave_scan_items<F>(heads, x, lane, &cnt);
+    tile_hand_over<F>(part, cnt, lane, wave, s_part, s_cnt, &before, &open, &total);
+    if (threadIdx.x == 0) {
+      const uint32_t first = tile == 0 ? head0 : 0u;  // position 0 is the plan's, not the count's
+      if (total - first != tile_cnt[tile]) atomicOr(err, 1u);
+      tile_open[tile] = open;
+    }
+    __syncthreads();
+  }
+}
+
+// One workgroup, chunked over adjacent tiles as k_run_scan: a segmented
+// exclusive scan of tile_open in tile order, a tile with a head starting anew.
+// With S(t) = tile_open[t] when tile t has a head, else S(t - 1) + tile_open[t]
+// (S(-1) the identity): tile_in[t] = S(t - 1), *trail = S(tiles - 1) in the
+// caller's bits.  A thread folds its chunk, the chunks' (value, has a head)
+// pairs are scanned in LDS, and the thread walks its chunk again from what the
+// chunks before it leave open.
+__global__ __launch_bounds__(kRunScanBlock) void k_run_scan_chain(int64_t tiles, uint32_t head0,
+                                                                  const uint32_t* __restrict__ tile_cnt,
+                                                                  const uint64_t* __restrict__ tile_open, int F,
+                                                                  int val_type, uint64_t* __restrict__ tile_in,
+                                                                  uint64_t* __restrict__ trail) {
+  __shared__ uint64_t s_v[kRunScanBlock];
+  __shared__ uint32_t s_h[kRunScanBlock];
+  const int t = (int)threadIdx.x;
+  const int64_t chunk = (tiles + kRunScanBlock - 1) / kRunScanBlock;
+  const int64_t lo = t * chunk < tiles ? t * chunk : tiles;
+  const int64_t hi = lo + chunk < tiles ? lo + chunk : tiles;
+  uint64_t acc = red_identity(F);
+  uint32_t has = 0;
+  for (int64_t i = lo; i < hi; ++i) {
+    const uint32_t h = tile_cnt[i] + (i == 0 ? head0 : 0u);
+    acc = h ? tile_open[i] : red(F, acc, tile_open[i]);
+    has |= h;
+  }
+  s_v[t] = acc;
+  s_h[t] = has;
+  __syncthreads();
+  for (int off = 1; off < kRunScanBlock; off <<= 1) {
+    uint64_t v = s_v[t];
+    uint32_t h = s_h[t];
+    if (t >= off && !h) {
+      v = red(F, s_v[t - off], v);
+      h = s_h[t - off];
+    }
+    __syncthreads();
+    s_v[t] = v;
+    s_h[t] = h;
+    __syncthreads();
+  }
+  uint64_t open = t ? s_v[t - 1] : red_identity(F);
+  for (int64_t i = lo; i < hi; ++i) {
+    tile_in[i] = open;
+    const uint32_t h = tile_cnt[i] + (i == 0 ? head0 : 0u);
+    open = h ? tile_open[i] : red(F, open, tile_open[i]);
+  }
+  // the chunks after the last tile are empty: the last thread holds S(tiles - 1)
+  if (t == kRunScanBlock - 1) *trail = red_store(F, open, key_form(val_type, 0));
+}
+
+// The result of every record, one read of A and one write: out[i] (SINK
+// kScanColumn, 8-byte elements) or the record {key (kScanKeep) or old value
+// (kScanByValue), result} at out[i] (another buffer than A: a wave reads
+// A[wave0 - 1]).  A result is a fold of up to three parts, in one association:
+//   ((carry + tile_in[t]) + s)  for a record in front of the rank's first head (i < lead)
+//   (tile_in[t] + s)            for a later record in front of its tile's first head
+//   s                           otherwise
+// with s the scan inside the tile, itself (what the waves before leave open,
+// folded in wave order) + (the value of lane 63 of the item before + the
+// scan across the item's lanes), each part only where no head lies between.
+// The counting kinds scan ones: with c the inclusive count, kSkCount gives
+// c - 1 and kSkStart the record's global position - (c - 1).
+// Every store is at the position its record was loaded from: a store
+// instruction writes adjacent elements across the lanes, like the loads.  The
+// recount guards every store of the tile, as in k_run_write.
+template <int K, int SINK>
+__global__ __launch_bounds__(kRunBlock) void k_run_scan_write(const Elem* __restrict__ A, void* __restrict__ out,
+                                                              int64_t here, int64_t tiles, int64_t gbase,
+                                                              uint32_t head0, int64_t lead,
+                                                              const uint32_t* __restrict__ tile_cnt,
+                                                              const uint64_t* __restrict__ tile_in, int val_type,
+                                                              uint64_t carry_bits, uint32_t* __restrict__ err) {
+  constexpr int F = sk_form(K);
+  __shared__ uint64_t s_part[kRunWaves];
+  __shared__ uint32_t s_cnt[kRunWaves];
+  const int lane = run_lane(), wave = (int)(threadIdx.x >> 6);
+  const KeyForm form = key_form(val_type, 0);
+  const uint64_t carry = red_load(F, carry_bits, form);
+  const uint64_t le = ~0ull >> (63 - lane);  // the lanes at or below this one
+  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    uint64_t key[kRunItems], val[kRunItems], x[kRunItems], heads[kRunItems];
+    const int64_t wave0 = tile * kTile + (int64_t)wave * kRunWaveRecs;
+    wave_heads<(K < kSkCount || SINK == kScanByValue)>(A, here, wave0, head0 != 0, key, val, heads);
+#pragma unroll
+    for (int j = 0; j < kRunItems; ++j) x[j] = val[j];
+    scan_operands<K>(x, wave0, here, lane, form);
+    uint32_t cnt, before, total;
+    uint64_t open;
+    const uint64_t part = wave_scan_items<F>(heads, x, lane, &cnt);
+    const uint64_t cw = tile_hand_over<F>(part, cnt, lane, wave, s_part, s_cnt, &before, &open, &total);
+    const uint32_t first = tile == 0 ? head0 : 0u;  // position 0 is the plan's, not the count's
+    if (total - first != tile_cnt[tile]) {
+      if (threadIdx.x == 0) atomicOr(err, 1u);
+    } else {
+      const uint64_t tin = tile_in[tile];
+      const uint64_t tc = red<F>(carry, tin);
+      bool pre = true;  // no head of this wave in the items before j
+#pragma unroll
+      for (int j = 0; j < kRunItems; ++j) {
+        const int64_t i = wave0 + j * 64 + lane;
+        uint64_t v = x[j];
+        if (pre && (heads[j] & le) == 0) {  // no head of this wave at or below the record
+          v = red<F>(cw, v);
+          if (before == 0) v = red<F>(i < lead ? tc : tin, v);  // nor of the tile
+        }
+        uint64_t res;
+        if constexpr (K == kSkCount) res = v - 1;
+        else if constexpr (K == kSkStart) res = (uint64_t)(gbase + i) - (v - 1);
+        else res = red_store(F, v, form);
+        if (i < here) {
+          if constexpr (SINK == kScanColumn) {
+            static_cast<uint64_t*>(out)[i] = res;
+          } else {
+            const u64x2 rec = {SINK == kScanKeep ? key[j] : val[j], res};
+            *reinterpret_cast<u64x2*>(static_cast<Elem*>(out) + i) = rec;
+          }
+        }
+        pre = pre && heads[j] == 0;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+template <int K>
+void launch_scan_write_kind(int sink, dim3 grid, hipStream_t s, const Elem* A, void* out, int64_t here, int64_t tiles,
+                            int64_t gbase, uint32_t head0, int64_t lead, const uint32_t* tile_cnt,
+                            const uint64_t* tile_in, int val_type, uint64_t carry, uint32_t* err) {
+  const dim3 block(kRunBlock);
+  if (sink == kScanColumn)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_run_scan_write<K, kScanColumn>), grid, block, 0, s, A, out, here, tiles,
+                       gbase, head0, lead, tile_cnt, tile_in, val_type, carry, err);
+  else if (sink == kScanKeep)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_run_scan_write<K, kScanKeep>), grid, block, 0, s, A, out, here, tiles, gbase,
+                       head0, lead, tile_cnt, tile_in, val_type, carry, err);
+  else
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_run_scan_write<K, kScanByValue>), grid, block, 0, s, A, out, here, tiles,
+                       gbase, head0, lead, tile_cnt, tile_in, val_type, carry, err);
+}
+
+int scan_kind(int op, int val_type) {
+  return op == kScanCount ? (int)kSkCount : op == kScanStart ? (int)kSkStart : red_form(op, val_type);
+}
+
 int run_grid(int64_t work, int block) {
   const int64_t g = (work + block - 1) / block;
   return (int)(g < 1 ? 1 : (g > kRunGridCap ? kRunGridCap : g));
@@ -629,6 +893,81 @@ hipError_t launch_run_reduce(const Elem* A, int64_t here, int head0, const uint3
   }
   hipLaunchKernelGGL(k_run_carry, dim3(1), dim3(kRunScanBlock), 0, s, tiles, (uint32_t)head0, tile_cnt, tile_base,
                      tile_lead, F, val_type, tail, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_run_scan_plan(const Elem* A, int64_t here, int head0, const uint32_t* tile_cnt, int op,
+                                int val_type, uint64_t* tile_open, uint64_t* tile_in, uint64_t* trail,
+                                uint32_t* err, hipStream_t s) {
+  if (!scan_valid(op, val_type) || (head0 != 0 && head0 != 1) || here <= 0 || !A || !tile_cnt || !tile_open ||
+      !tile_in || !trail || !err)
+    return hipErrorInvalidValue;
+  const int64_t tiles = run_tiles(here);
+  const dim3 grid(run_grid(tiles, 1)), block(kRunBlock);
+  switch (scan_kind(op, val_type)) {
+    case kSkAdd:
+      hipLaunchKernelGGL(k_run_scan_tile<kSkAdd>, grid, block, 0, s, A, here, tiles, (uint32_t)head0, tile_cnt,
+                         val_type, tile_open, err);
+      break;
+    case kSkFadd:
+      hipLaunchKernelGGL(k_run_scan_tile<kSkFadd>, grid, block, 0, s, A, here, tiles, (uint32_t)head0, tile_cnt,
+                         val_type, tile_open, err);
+      break;
+    case kSkMin:
+      hipLaunchKernelGGL(k_run_scan_tile<kSkMin>, grid, block, 0, s, A, here, tiles, (uint32_t)head0, tile_cnt,
+                         val_type, tile_open, err);
+      break;
+    case kSkMax:
+      hipLaunchKernelGGL(k_run_scan_tile<kSkMax>, grid, block, 0, s, A, here, tiles, (uint32_t)head0, tile_cnt,
+                         val_type, tile_open, err);
+      break;
+    default:  // both counting kinds scan ones
+      hipLaunchKernelGGL(k_run_scan_tile<kSkCount>, grid, block, 0, s, A, here, tiles, (uint32_t)head0, tile_cnt,
+                         val_type, tile_open, err);
+      break;
+  }
+  hipLaunchKernelGGL(k_run_scan_chain, dim3(1), dim3(kRunScanBlock), 0, s, tiles, (uint32_t)head0, tile_cnt,
+                     tile_open, scan_form(op, val_type), val_type, tile_in, trail);
+  return hipGetLastError();
+}
+
+hipError_t launch_run_scan_write(const Elem* A, int64_t here, int64_t gbase, int head0, int64_t lead,
+                                 const uint32_t* tile_cnt, const uint64_t* tile_in, int op, int val_type,
+                                 uint64_t carry, int sink, void* out, uint32_t* err, hipStream_t s) {
+  if (!scan_valid(op, val_type) || (head0 != 0 && head0 != 1) || lead < 0 || lead > here || (head0 && lead != 0) ||
+      (sink != kScanColumn && sink != kScanKeep && sink != kScanByValue) || !A || !out || out == A || !tile_cnt ||
+      !tile_in || !err)
+    return hipErrorInvalidValue;
+  if (here <= 0) return hipSuccess;
+  const int64_t tiles = run_tiles(here);
+  const dim3 grid(run_grid(tiles, 1));
+  const uint32_t h0 = (uint32_t)head0;
+  switch (scan_kind(op, val_type)) {
+    case kSkAdd:
+      launch_scan_write_kind<kSkAdd>(sink, grid, s, A, out, here, tiles, gbase, h0, lead, tile_cnt, tile_in, val_type,
+                                     carry, err);
+      break;
+    case kSkFadd:
+      launch_scan_write_kind<kSkFadd>(sink, grid, s, A, out, here, tiles, gbase, h0, lead, tile_cnt, tile_in, val_type,
+                                      carry, err);
+      break;
+    case kSkMin:
+      launch_scan_write_kind<kSkMin>(sink, grid, s, A, out, here, tiles, gbase, h0, lead, tile_cnt, tile_in, val_type,
+                                     carry, err);
+      break;
+    case kSkMax:
+      launch_scan_write_kind<kSkMax>(sink, grid, s, A, out, here, tiles, gbase, h0, lead, tile_cnt, tile_in, val_type,
+                                     carry, err);
+      break;
+    case kSkCount:
+      launch_scan_write_kind<kSkCount>(sink, grid, s, A, out, here, tiles, gbase, h0, lead, tile_cnt, tile_in,
+                                       val_type, carry, err);
+      break;
+    default:
+      launch_scan_write_kind<kSkStart>(sink, grid, s, A, out, here, tiles, gbase, h0, lead, tile_cnt, tile_in,
+                                       val_type, carry, err);
+      break;
+  }
   return hipGetLastError();
 }
 

@@ -25,7 +25,11 @@ groups of equal keys come from ``unique(keys)``, or ``World.count_runs`` /
 column (sum, min, max) from ``group_reduce(keys, values)``, or
 ``World.plan_reduce`` / ``World.store_reduce``, and the group of every record
 (unique's inverse, a dense rank) from ``unique(keys, return_inverse=True)`` or
-``dense_rank(keys)``, or ``World.label_runs``.  The k-th key and the k best
+``dense_rank(keys)``, or ``World.label_runs``, and one number per record from
+the records in front of it in its group (a running sum, min or max, its place
+in the group, the group's start) from ``group_scan(keys, values)``,
+``cumcount(keys)`` and ``rank(keys)``, or ``World.plan_scan`` /
+``World.store_scan`` / ``World.scan_runs``.  The k-th key and the k best
 records need no sort: ``kth(keys, k)`` and ``topk(keys, k)``, or ``World.select`` /
 ``World.store_select``.  torch is imported only inside those
 functions.  A process that uses them imports torch before the first call into
@@ -82,6 +86,9 @@ ORDER_DESCENDING = 1
 REDUCE_SUM, REDUCE_MIN, REDUCE_MAX = range(3)
 # What a labelled record becomes (LSB_LABEL_*): {key, id} or {old value, id}.
 LABEL_KEEP, LABEL_BY_VALUE = 0, 1
+# Scans within the runs (LSB_SCAN_*): the reductions' ops per record, its place
+# in its run, and its run's first global position.
+SCAN_SUM, SCAN_MIN, SCAN_MAX, SCAN_COUNT, SCAN_START = range(5)
 
 
 class LsbError(RuntimeError):
@@ -202,6 +209,10 @@ def _lib() -> ctypes.CDLL:
             "lsb_plan_reduce": (i32, [vp, i32, i32]),
             "lsb_store_reduce": (i32, [vp, i32, i64, vp, P64]),
             "lsb_label_runs": (i32, [vp, i32]),
+            "lsb_plan_run_carries": (i32, [i64, i32, vp, i32, i32, vp, vp]),
+            "lsb_plan_scan": (i32, [vp, i32, i32]),
+            "lsb_store_scan": (i32, [vp, i32, i64, vp, P64]),
+            "lsb_scan_runs": (i32, [vp, i32]),
             "lsb_plan_select": (i32, [i64, i32, i64, vp, vp, vp, vp]),
             "lsb_select": (i32, [vp, i64, ctypes.POINTER(ctypes.c_uint64), P64, P64, vp, vp]),
             "lsb_store_select": (i32, [vp, i32, i64, vp, i32, i32, vp, i32, P64]),
@@ -545,6 +556,97 @@ def group_reduce(keys, values, op: str = "sum", descending: bool = False, ranks:
     return out_k, out_v
 
 
+def group_scan(keys, values, op: str = "sum", descending: bool = False, ranks: int = 1, radix_bits: int = 8,
+               key_type: Optional[int] = None):
+    """A running reduction inside every group, in input order: out[i] = op
+    ("sum", "min", "max") over values[j] of every j <= i whose key has the bits
+    of keys[i] (groupby(keys).cumsum(), cummin(), cummax()), in the values'
+    dtype (int64, float64, or uint64 where torch has it).
+
+    Integer sums wrap; a float64 sum is reproducible for given inputs and
+    ranks; min and max follow lsb.h's float order.  keys as for sort(); values
+    the same length.  The inputs are left untouched, the output is a fresh
+    tensor.  sort() gives the sorted keys and the stable argsort, torch gathers
+    the values by it, one World(n, ranks) loads the two sorted columns, counts
+    the runs, plans the scan and stores each rank's results, and torch
+    scatters them back by the argsort."""
+    import torch
+    _check_column(keys, "keys")
+    kt = _key_type_of(keys, key_type)
+    _check_column(values, "values", keys.device)
+    vt = _value_type_of(values)
+    if values.numel() != keys.numel():
+        raise ValueError("keys and values differ in length")
+    ops = {"sum": SCAN_SUM, "min": SCAN_MIN, "max": SCAN_MAX}
+    if op not in ops:
+        raise ValueError(f"op {op!r}: not one of {sorted(ops)}")
+    if ranks < 1:
+        raise ValueError("ranks")
+    n = keys.numel()
+    out = torch.empty_like(values)
+    if n == 0:
+        return out
+    sorted_keys, idx = sort(keys, None, descending=descending, ranks=ranks, radix_bits=radix_bits, key_type=kt)
+    # torch indexes int64 where it does not uint64: the gather and the scatter move bits
+    gathered = values.view(torch.int64)[idx]
+    scanned = torch.empty(n, dtype=torch.int64, device=keys.device)
+    dev = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
+    with World(n, ranks=ranks, devices=[dev] * ranks, radix_bits=radix_bits) as w:
+        blocks = [(r, r * w.per, w.here(r)) for r in range(ranks) if w.here(r)]
+        for r, lo, h in blocks:
+            w.load_columns(r, sorted_keys[lo:lo + h], gathered[lo:lo + h], descending=descending, key_type=kt)
+        w.count_runs()
+        w.plan_scan(ops[op], vt)
+        for r, lo, h in blocks:
+            w.store_scan(r, scanned[lo:lo + h])
+    out.view(torch.int64)[idx] = scanned
+    return out
+
+
+def _scan_positions(keys, op: int, descending: bool, ranks: int, radix_bits: int, key_type: Optional[int]):
+    """SCAN_COUNT or SCAN_START of every key, in input order (int64): the
+    inverse's route with the scan's result in place of the run id."""
+    import torch
+    _check_column(keys, "keys")
+    kt = _key_type_of(keys, key_type)
+    if ranks < 1:
+        raise ValueError("ranks")
+    n = keys.numel()
+    out = torch.empty(n, dtype=torch.int64, device=keys.device)
+    if n == 0:
+        return out
+    dev = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
+    with World(n, ranks=ranks, devices=[dev] * ranks, radix_bits=radix_bits) as w:
+        blocks = [(r, r * w.per, w.here(r)) for r in range(ranks) if w.here(r)]
+        for r, lo, h in blocks:
+            w.load_columns(r, keys[lo:lo + h], None, descending=descending, key_type=kt)
+        w.my_sort()
+        w.count_runs()
+        w.plan_scan(op, KEY_U64)
+        w.scan_runs(LABEL_BY_VALUE)
+        w.my_sort()
+        for r, lo, h in blocks:
+            w.store_columns(r, None, out[lo:lo + h])
+    return out
+
+
+def cumcount(keys, descending: bool = False, ranks: int = 1, radix_bits: int = 8, key_type: Optional[int] = None):
+    """The number of earlier records with the same key, for every key of a
+    device column: int64 of the input's length (groupby(keys).cumcount(),
+    ROW_NUMBER() OVER (PARTITION BY key) - 1).  Keys are equal when their bits
+    are.  keys as for sort(); the input is left untouched."""
+    return _scan_positions(keys, SCAN_COUNT, descending, ranks, radix_bits, key_type)
+
+
+def rank(keys, descending: bool = False, ranks: int = 1, radix_bits: int = 8, key_type: Optional[int] = None):
+    """The 0-based competition rank of every key of a device column: int64 of
+    the input's length, rank[i] = the number of records whose key is strictly
+    below keys[i] (descending: above it), in the float order of lsb.h; ties
+    share the lowest rank (SQL RANK() - 1, rankdata(method="min") - 1).  keys
+    as for sort(); the input is left untouched."""
+    return _scan_positions(keys, SCAN_START, descending, ranks, radix_bits, key_type)
+
+
 def _key_tensor(bits: int, like):
     """A 1-element tensor of like's dtype and device whose bits are `bits`."""
     import torch
@@ -675,6 +777,21 @@ def plan_run_tails(n: int, P: int, summary: np.ndarray, op: int, val_type: int, 
     _check(_lib().lsb_plan_run_tails(n, P, summary.ctypes.data, op, val_type, lead.ctypes.data, tail.ctypes.data),
            "lsb_plan_run_tails")
     return tail
+
+
+def plan_run_carries(n: int, P: int, summary: np.ndarray, op: int, val_type: int, trail: np.ndarray) -> np.ndarray:
+    """lsb_plan_run_carries, the host planner of the scans within the runs:
+    summary as for plan_runs, trail[s] = op over the operands of rank s's
+    records from its last head on (uint64 bits) -> carry[P] (uint64 bits),
+    what the ranks before r add to r's leading run."""
+    summary = np.ascontiguousarray(summary, dtype=np.uint64)
+    trail = np.ascontiguousarray(trail, dtype=np.uint64)
+    if summary.shape != (P, 4) or trail.shape != (P,):
+        raise ValueError("summary must be P x 4, trail P")
+    carry = np.zeros(P, dtype=np.uint64)
+    _check(_lib().lsb_plan_run_carries(n, P, summary.ctypes.data, op, val_type, trail.ctypes.data,
+                                       carry.ctypes.data), "lsb_plan_run_carries")
+    return carry
 
 
 def get_unique_id() -> bytes:
@@ -943,6 +1060,39 @@ class World:
         my_sort() after it puts the ids in input order: the inverse).  The
         records change, so the plans end: count_runs again before a store."""
         _check(_lib().lsb_label_runs(self._h, mode), "lsb_label_runs")
+
+    def plan_scan(self, op: int, val_type: int) -> None:
+        """lsb_plan_scan: after count_runs, what the earlier tiles and ranks
+        add to every record's run under op (SCAN_SUM, SCAN_MIN, SCAN_MAX over
+        the values read as KEY_U64, KEY_I64 or KEY_F64; SCAN_COUNT, SCAN_START
+        with KEY_U64); a collective in a one-rank-per-process world.
+        store_scan and scan_runs need it."""
+        _check(_lib().lsb_plan_scan(self._h, op, val_type), "lsb_plan_scan")
+
+    def store_scan(self, rank: int, out) -> int:
+        """lsb_store_scan: out[i] = the planned scan's result for the record
+        at slot i of `rank`.  out: a 1-D contiguous CUDA torch tensor of
+        8-byte elements that holds at least the rank's records; -> that
+        number."""
+        import torch
+        _check_column(out, "out")
+        if out.element_size() != 8:
+            raise ValueError("out: not 8-byte elements")
+        cap = out.numel()
+        if cap == 0:  # an empty tensor has no address (cap 0: never written)
+            out = out.new_empty(1)
+        torch.cuda.current_stream(out.device).synchronize()
+        count = ctypes.c_int64()
+        _check(_lib().lsb_store_scan(self._h, rank, cap, out.data_ptr(), ctypes.byref(count)), "lsb_store_scan")
+        return int(count.value)
+
+    def scan_runs(self, mode: int) -> None:
+        """lsb_scan_runs: after plan_scan, every record of every local rank
+        gets the scan's result as its value: LABEL_KEEP leaves the key,
+        LABEL_BY_VALUE makes the old value the key (with index values, a
+        my_sort() after it puts the results in input order).  The records
+        change, so the plans end."""
+        _check(_lib().lsb_scan_runs(self._h, mode), "lsb_scan_runs")
 
     def select(self, k: int) -> dict:
         """lsb_select: the key the stable sort would put at global position k

@@ -361,7 +361,7 @@ int  lsb_store_columns(lsb_ctx_t* ctx, int rank, int64_t off, int64_t cnt,
  * every rank of the world.  n == 0: *total = 0, nothing is launched.  The
  * first call allocates 12 bytes per 4096 records of scratch on each rank.
  * The plan stays valid until lsb_generate, lsb_generate_ex, lsb_copy_in,
- * lsb_load_columns, lsb_sort, lsb_pass or lsb_label_runs is called.  In a one-rank-per-
+ * lsb_load_columns, lsb_sort, lsb_pass, lsb_label_runs or lsb_scan_runs is called.  In a one-rank-per-
  * process world lsb_copy_in and lsb_load_columns are local calls and drop the
  * plan of the calling process only, while the other ranks' plans depend on
  * its records (a run's count reaches into later ranks): after any rank has
@@ -515,6 +515,114 @@ int  lsb_store_reduce(lsb_ctx_t* ctx, int rank, int64_t cap, void* out_dev, int6
 #define LSB_LABEL_BY_VALUE 1
 int  lsb_label_runs(lsb_ctx_t* ctx, int mode);
 
+/* A scan within the runs: one number per record, from the records in front of
+ * it in its run (a running sum, min or max of a group's values:
+ * groupby().cumsum(), a window aggregate OVER (PARTITION BY key ORDER BY
+ * position); the record's place inside its group: cumcount, ROW_NUMBER(); the
+ * group's start: RANK()), across tile and rank boundaries.  Runs, key equality
+ * and the global position order are those of "runs of equal keys" above.  For
+ * the record at global position g whose run starts at global position s <= g:
+ *   LSB_SCAN_SUM, LSB_SCAN_MIN, LSB_SCAN_MAX (== LSB_REDUCE_*)
+ *                    op over the values of the positions s .. g, the 64 value
+ *                    bits read as val_type (LSB_KEY_U64, LSB_KEY_I64 or
+ *                    LSB_KEY_F64), as for lsb_plan_reduce
+ *   LSB_SCAN_COUNT   g - s: the run's records in front of this one (0-based;
+ *                    cumcount, ROW_NUMBER() - 1).  No operand: val_type must
+ *                    be LSB_KEY_U64
+ *   LSB_SCAN_START   s: the global position of the run's first record
+ *                    (RANK() - 1 on a sorted array; starts_dev[id] of
+ *                    lsb_store_runs).  No operand: val_type must be LSB_KEY_U64
+ * The rules of the reductions carry over: integer sums wrap modulo 2^64; MIN
+ * and MAX follow lsb_key_encode's order, the float order included, and return
+ * one of the run's values bit for bit; the F64 SUM combines with the identity
+ * -0.0 (a run of -0.0 values scans to -0.0), the code fixes the order and the
+ * association of every addition (no float atomics, no timing), and for given
+ * (n, P, records) the result is bit-identical from call to call; it may differ
+ * between values of P.  The association: with t the record's 4096-record tile
+ * of its rank, result = ((carry[rank] + in(t)) + scan inside t), where in(t)
+ * is what the rank's earlier tiles add to the run open at t's first record
+ * (folded forwards in tile order) and carry[rank] what the earlier ranks add
+ * to the rank's leading run (folded forwards in rank order); a part is
+ * present only where no head lies between it and the record.
+ * The last record of a run carries what lsb_store_reduce writes for that run,
+ * bit for bit for MIN, MAX and the integer SUM; for the F64 SUM the two agree
+ * within the rounding of two summation orders (the reduction folds backwards
+ * from the run's tail, the scan forwards).
+ *
+ * lsb_plan_run_carries: the host planner, pure host code, the mirror of
+ * lsb_plan_run_tails.  summary as for lsb_plan_runs (and checked the same
+ * way); trail[s] = op over the operands of rank s's records from its last
+ * head on (all its records when it has none; slot 0 is a head when a run
+ * starts there); ignored for empty ranks.  carry[r] = the left fold, in
+ * increasing rank order and from the identity, of trail[s] over the ranks
+ * s < r whose last run is r's leading run: the walk goes down from r - 1,
+ * skips empty ranks, stops at a rank whose last key is not r's first key,
+ * takes the rank, and stops after a rank that has a head of its own (inner
+ * > 0, or a run starts at its slot 0).  The identity for empty ranks and for
+ * ranks whose slot 0 starts a run.  For COUNT and START every record's
+ * operand is 1 and the fold the u64 sum: carry[r] = the records of r's
+ * leading run on earlier ranks.  LSB_ERR_INVALID on a null argument, n < 0, P
+ * outside [1, 64], an unknown op, a value type outside {U64, I64, F64}, COUNT
+ * or START with a type other than U64, or a summary lsb_plan_runs refuses.
+ *
+ * lsb_plan_scan: collective in one-rank-per-process contexts, like
+ * lsb_plan_reduce; needs a valid run plan (LSB_ERR_STATE otherwise).  An
+ * unknown op or type returns LSB_ERR_INVALID before anything is launched or
+ * gathered.  n == 0 returns LSB_OK and launches nothing.  Every non-empty
+ * local rank, on its own stream, reads its A once (what each tile leaves open
+ * at its end), then scans those words in one workgroup (what each tile takes
+ * in, and the rank's trail word); the trail words are gathered (8 bytes per
+ * rank), lsb_plan_run_carries runs on them, and the carries, op and val_type
+ * are kept in the context.  LSB_ERR_STATE after the gather when a local
+ * rank's A was changed behind the library's back since lsb_count_runs; the
+ * run plan is then dropped.  The scan plan dies with the run plan; a later
+ * lsb_plan_scan replaces it; it is independent of the reduce plan, and a
+ * caller may hold both.  The first call allocates, on each rank, 16 bytes per
+ * 4096 records and 16 bytes more of scratch (freed with the context;
+ * lsb_rank_footprint does not model it, as it does not the reduce scratch).
+ *
+ * lsb_store_scan: local, no collective; needs a scan plan (LSB_ERR_STATE
+ * otherwise).  Reads rank's A once more and writes out_dev[i] = the result of
+ * the record at slot i, i in [0, here(rank)): a column of cap 8-byte elements
+ * in slot order.  A is untouched and the plans stay: several ops can be
+ * planned and stored one after another from one lsb_count_runs.  *count (may
+ * be NULL) = here(rank); cap < here(rank) returns LSB_ERR_INVALID with *count
+ * set and nothing written.  An empty rank returns LSB_OK, launches nothing
+ * and does not examine out_dev.  LSB_ERR_INVALID, before any kernel is
+ * launched: bad rank, cap < 0, null out_dev, and the pointer checks of
+ * lsb_load_columns over cap 8-byte elements.  The column is written in 8-byte
+ * accesses, adjacent lanes writing adjacent elements (a record's result stays
+ * in the lane that loaded the record), whatever its alignment beyond 8 bytes.
+ * LSB_ERR_STATE after the kernel: A was changed behind the library's back
+ * since lsb_count_runs; the output is then unspecified, nothing is written
+ * outside [0, here(rank)) and the plans are dropped.  Streams as
+ * lsb_store_runs.
+ *
+ * lsb_scan_runs: the records form, lsb_label_runs with the scan's result in
+ * place of the run id.  LSB_LABEL_KEEP: each record becomes {key, result};
+ * LSB_LABEL_BY_VALUE: {key = its old value, value = result}.  Local, no
+ * collective; needs a scan plan (LSB_ERR_STATE otherwise).  One call covers
+ * every local rank, each on its own stream, into its second record buffer,
+ * which then becomes A.  A successful call ends the run, reduce, scan and
+ * select plans.  An unknown mode returns LSB_ERR_INVALID and leaves the plans
+ * as they were.  n == 0 returns LSB_OK.  LSB_ERR_STATE after the kernels: a
+ * local rank's A was changed since lsb_count_runs; then no rank is swapped,
+ * every A is what it was, and the plans are dropped.
+ * cumcount or rank in input order, the recipe of the inverse: load the keys
+ * with vals_dev NULL, lsb_sort, lsb_count_runs, lsb_plan_scan(LSB_SCAN_COUNT
+ * or LSB_SCAN_START, LSB_KEY_U64), lsb_scan_runs(LSB_LABEL_BY_VALUE), lsb_sort
+ * again, lsb_store_columns(keys_dev NULL, vals_dev). */
+#define LSB_SCAN_SUM   0
+#define LSB_SCAN_MIN   1
+#define LSB_SCAN_MAX   2
+#define LSB_SCAN_COUNT 3
+#define LSB_SCAN_START 4
+int  lsb_plan_run_carries(int64_t n_total, int num_ranks, const uint64_t* summary,
+                          int op, int val_type, const uint64_t* trail, uint64_t* carry);
+int  lsb_plan_scan(lsb_ctx_t* ctx, int op, int val_type);
+int  lsb_store_scan(lsb_ctx_t* ctx, int rank, int64_t cap, void* out_dev, int64_t* count);
+int  lsb_scan_runs(lsb_ctx_t* ctx, int mode);
+
 /* ---- the k-th key and the first k + 1 records, without a sort -------------- */
 /* The commonest question that needs no full sort: the k-th smallest key
  * (median, percentile, threshold) and the k best records (top-k with their
@@ -560,7 +668,7 @@ int  lsb_label_runs(lsb_ctx_t* ctx, int mode);
  * rank of the world.  Every output may be NULL.
  * The context keeps the plan (pivot and the per-rank counts) until
  * lsb_generate, lsb_generate_ex, lsb_copy_in, lsb_load_columns, lsb_sort,
- * lsb_pass or lsb_label_runs is called: the calls that end a run plan, and
+ * lsb_pass, lsb_label_runs or lsb_scan_runs is called: the calls that end a run plan, and
  * the note on one-rank-per-process worlds there applies unchanged.  The run
  * plan and the reduce plan are left alone, and lsb_count_runs,
  * lsb_store_runs, lsb_plan_reduce and lsb_store_reduce leave this plan alone.
