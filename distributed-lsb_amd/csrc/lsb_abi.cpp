@@ -303,6 +303,7 @@ int lsb_generate_ex(lsb_ctx_t* c, int dist, double param) {
   }
   runs_invalidate(c);
   select_invalidate(c);
+  search_invalidate(c);
   c->keygen = g;
   for (Rank& r : c->ranks) {
     HIP_TRY(hipSetDevice(r.dev));
@@ -324,6 +325,7 @@ int lsb_copy_in(lsb_ctx_t* c, int rank, int64_t off, int64_t cnt, const lsb_elem
   if (cnt == 0) return LSB_OK;
   runs_invalidate(c);
   select_invalidate(c);
+  search_invalidate(c);
   HIP_TRY(hipSetDevice(r->dev));
   HIP_TRY(hipStreamSynchronize(r->stream));
   HIP_TRY(hipMemcpy(r->A + off, host, (size_t)cnt * sizeof(Elem), hipMemcpyHostToDevice));
@@ -377,6 +379,7 @@ int lsb_load_columns(lsb_ctx_t* c, int rank, int64_t off, int64_t cnt, const voi
   if (!keys_dev) return fail(LSB_ERR_INVALID, "lsb_load_columns", "null keys");
   runs_invalidate(c);
   select_invalidate(c);
+  search_invalidate(c);
   HIP_TRY(hipStreamSynchronize(r->stream));
   // The value of a record without one: its global index (mpi/mpi_lsbsort.cpp:650-656).
   const uint64_t val0 = (uint64_t)r->rank * (uint64_t)c->per + (uint64_t)off;
@@ -420,6 +423,7 @@ int lsb_pass(lsb_ctx_t* c, int digit) {
   if (digit < 0 || digit >= 64 / c->bits) return fail(LSB_ERR_INVALID, "lsb_pass", "digit");
   runs_invalidate(c);
   select_invalidate(c);
+  search_invalidate(c);
   // Filed under the digit's own local passes (a 64-bit digit: the whole sort).
   c->pass_cursor = c->bits == 64 ? 0 : digit * (c->bits / lsb::kDigitBits);
   const int rc = do_pass(c, digit);
@@ -478,6 +482,7 @@ int lsb_sort(lsb_ctx_t* c) {
     return fail(LSB_ERR_STATE, "lsb_sort", "an earlier sort failed and left packed records in A; load the input again");
   runs_invalidate(c);
   select_invalidate(c);
+  search_invalidate(c);
   const int rc = sort_body(c);
   if (rc != LSB_OK) quiesce(c);
   return rc;

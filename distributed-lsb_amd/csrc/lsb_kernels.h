@@ -621,4 +621,19 @@ hipError_t launch_select_write(const Elem* A, int64_t here, uint64_t pivot, int6
                                const uint32_t* tile_cnt, const int64_t* tile_base, void* keys, int key_type, int flags,
                                void* vals, int val_bytes, uint32_t* err, hipStream_t s);
 
+// Searching a rank's sorted records for a column of queries (lsb_search.hip;
+// lsb_search, include/lsb.h).  == LSB_SEARCH_*.
+constexpr int kSearchLower = 0, kSearchUpper = 1, kSearchCount = 2, kSearchAdd = 4;
+inline bool search_mode_valid(int mode) { return mode >= 0 && (mode & ~kSearchAdd) <= kSearchCount; }
+// One strided read of A (here > 0): fence[t] = the key of record t * kTile,
+// run_tiles(here) words.
+hipError_t launch_search_fence(const Elem* A, int64_t here, uint64_t* fence, hipStream_t s);
+// out[i] = (mode & kSearchAdd ? out[i] : 0) + c_i for the m typed queries
+// (m > 0, here > 0), c_i the records of A[0, here) with key <, <= or == the
+// encoded query; fence as launch_search_fence left it.  Every record index
+// probed lies in [0, here), every fence index in [0, run_tiles(here)),
+// whatever A holds; every c_i in [0, here].
+hipError_t launch_search(const Elem* A, int64_t here, const uint64_t* fence, const void* queries, int64_t m,
+                         int key_type, int flags, int mode, int64_t* out, hipStream_t s);
+
 }  // namespace lsb

@@ -15,6 +15,8 @@
 //                     lsb_label_runs)
 //   lsb_select.cpp    the k-th key and the first k + 1 records without a sort
 //                     (lsb_plan_select, lsb_select, lsb_store_select)
+//   lsb_search.cpp    a column of queries against a rank's sorted records
+//                     (lsb_search)
 //   lsb_abi.cpp       the extern "C" entry points and the host planners
 //   lsb_xgeom.h       host-only exchange geometry (checked plan, waves); no
 //                     device header, so host tools can include it alone
@@ -168,6 +170,8 @@ struct Rank {
   uint64_t* sel_gather = nullptr;       // [P][kSelWords] all-gathered tables (one rank per process)
   uint32_t* sel_cnt = nullptr;          // [run_tiles(here)] keys below and equal to the pivot per tile (k_sel_count)
   int64_t* sel_tbase = nullptr;         // [run_tiles(here)][2] those of the tiles before (k_sel_scan)
+  // The search (lsb_search.cpp), allocated on first use.
+  uint64_t* search_fence = nullptr;     // [run_tiles(here)] the key of every tile's first record (k_search_fence)
   std::vector<int64_t> send_counts, send_displs, recv_counts, recv_displs;
 };
 
@@ -241,6 +245,10 @@ struct lsb_ctx {
   std::vector<int64_t> sel_below, sel_equal, sel_take, sel_base;  // [P]
   int sel_rounds = 0;
   int64_t sel_read = 0;
+  // Bit r: rank r's search_fence is that of its A (lsb_search builds it),
+  // until an entry point that can change A (search_invalidate).  lsb_select
+  // leaves A bit for bit and writes B only, so it keeps the fences.
+  uint64_t search_valid = 0;
   lsb::KeyGen keygen;
   std::vector<lsb_rt::PendingEvent> pending;
   std::vector<std::pair<int, hipEvent_t>> event_pool;  // (device, event) of finished timings
@@ -392,6 +400,8 @@ int check_ctx(const lsb_ctx* c);
 inline void runs_invalidate(lsb_ctx* c) { c->runs_valid = c->reduce_valid = c->scan_valid = false; }
 // A is about to change: lsb_store_select needs a new lsb_select.
 inline void select_invalidate(lsb_ctx* c) { c->select_valid = false; }
+// A is about to change: lsb_search builds a rank's fence table again.
+inline void search_invalidate(lsb_ctx* c) { c->search_valid = 0; }
 // A caller's column of cnt elements of `elem` bytes at p, before a kernel may
 // touch it (lsb_context.cpp): LSB_ERR_INVALID unless it is aligned to its element,
 // device (or managed) memory of the rank's device and inside its allocation.

@@ -347,6 +347,7 @@ int lsb_label_runs(lsb_ctx_t* c, int mode) {
   const int rc = c->n > 0 ? label_ranks(c, mode) : LSB_OK;
   runs_invalidate(c);
   select_invalidate(c);
+  search_invalidate(c);
   return rc;
 }
 
@@ -553,6 +554,7 @@ int lsb_scan_runs(lsb_ctx_t* c, int mode) {
   const int rc = c->n > 0 ? scan_ranks(c, mode) : LSB_OK;
   runs_invalidate(c);
   select_invalidate(c);
+  search_invalidate(c);
   return rc;
 }
 

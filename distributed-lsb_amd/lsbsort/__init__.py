@@ -31,8 +31,10 @@ in the group, the group's start) from ``group_scan(keys, values)``,
 ``cumcount(keys)`` and ``rank(keys)``, or ``World.plan_scan`` /
 ``World.store_scan`` / ``World.scan_runs``.  The k-th key and the k best
 records need no sort: ``kth(keys, k)`` and ``topk(keys, k)``, or ``World.select`` /
-``World.store_select``.  torch is imported only inside those
-functions.  A process that uses them imports torch before the first call into
+``World.store_select``.  A second column is searched against the sorted one
+(where each key would go, whether and how often it occurs) with
+``searchsorted(keys, queries)``, ``count_of`` and ``isin``, or ``World.search``.
+torch is imported only inside those functions.  A process that uses them imports torch before the first call into
 this module: the library then binds to the HIP runtime torch brought, and both
 see the same device memory.
 
@@ -89,6 +91,9 @@ LABEL_KEEP, LABEL_BY_VALUE = 0, 1
 # Scans within the runs (LSB_SCAN_*): the reductions' ops per record, its place
 # in its run, and its run's first global position.
 SCAN_SUM, SCAN_MIN, SCAN_MAX, SCAN_COUNT, SCAN_START = range(5)
+# What a search counts per query (LSB_SEARCH_*): the records below it, not
+# above it, equal to it; SEARCH_ADD or-ed in adds to the output column.
+SEARCH_LOWER, SEARCH_UPPER, SEARCH_COUNT, SEARCH_ADD = 0, 1, 2, 4
 
 
 class LsbError(RuntimeError):
@@ -217,6 +222,7 @@ def _lib() -> ctypes.CDLL:
             "lsb_select": (i32, [vp, i64, ctypes.POINTER(ctypes.c_uint64), P64, P64, vp, vp]),
             "lsb_store_select": (i32, [vp, i32, i64, vp, i32, i32, vp, i32, P64]),
             "lsb_get_last_select": (i32, [vp, ctypes.POINTER(ctypes.c_int), P64]),
+            "lsb_search": (i32, [vp, i32, i64, vp, i32, i32, i32, vp]),
             "lsb_sort": (i32, [vp]),
             "lsb_pass": (i32, [vp, i32]),
             "lsb_sync": (i32, [vp]),
@@ -245,8 +251,8 @@ def _lib() -> ctypes.CDLL:
         }
         for name, (res, args) in sig.items():
             # An older build given through LSB_LIBRARY (A/B timing against the
-            # parent commit) lacks the newest getter; calling it there raises.
-            if name == "lsb_get_last_packed_tile" and not hasattr(L, name):
+            # parent commit) lacks the newest entry points; calling them there raises.
+            if name in ("lsb_get_last_packed_tile", "lsb_search") and not hasattr(L, name):
                 continue
             fn = getattr(L, name)
             fn.restype = res
@@ -731,6 +737,74 @@ def topk(keys, k: int, largest: bool = True, sorted: bool = True, ranks: int = 1
     return values, indices
 
 
+_SEARCH_SIDES = {"left": SEARCH_LOWER, "right": SEARCH_UPPER, "count": SEARCH_COUNT}
+
+
+def _search(keys, queries, side: str, descending: bool, ranks: int, radix_bits: int, key_type: Optional[int],
+            assume_sorted: bool):
+    """One number per query (int64) from the sorted keys: World.search of every
+    non-empty rank, added up."""
+    import torch
+    if side not in _SEARCH_SIDES:
+        raise ValueError(f"side {side!r}: not one of {sorted(_SEARCH_SIDES)}")
+    _check_column(keys, "keys")
+    kt = _key_type_of(keys, key_type)
+    _check_column(queries, "queries", keys.device)
+    if _key_type_of(queries, key_type) != kt:
+        raise ValueError(f"queries of {queries.dtype} against keys of {keys.dtype}")
+    if ranks < 1:
+        raise ValueError("ranks")
+    n, m = keys.numel(), queries.numel()
+    out = torch.zeros(m, dtype=torch.int64, device=keys.device)
+    if n == 0 or m == 0:
+        return out
+    dev = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
+    with World(n, ranks=ranks, devices=[dev] * ranks, radix_bits=radix_bits) as w:
+        blocks = [(r, r * w.per, w.here(r)) for r in range(ranks) if w.here(r)]
+        for r, lo, h in blocks:
+            w.load_columns(r, keys[lo:lo + h], None, descending=descending, key_type=kt)
+        if not assume_sorted:
+            w.my_sort()
+        for i, (r, _, _) in enumerate(blocks):
+            w.search(r, queries, out, side=side, add=i > 0, descending=descending, key_type=kt)
+    return out
+
+
+def searchsorted(keys, queries, side: str = "left", descending: bool = False, ranks: int = 1, radix_bits: int = 8,
+                 key_type: Optional[int] = None, assume_sorted: bool = False):
+    """The position of every query in the stable sort of a device column:
+    int64 of the queries' length, out[i] = the number of keys below queries[i]
+    (side="left") or not above it (side="right"); descending: above, not below.
+
+    The order and equality are sort()'s, on the bits: -0.0 is below +0.0, NaNs
+    lie at both ends by sign and a NaN equals only its own bits, which is not
+    torch.searchsorted's float behaviour.  keys as for sort(); queries: a 1-D
+    contiguous CUDA tensor on the same device whose dtype maps to the same key
+    type (ValueError otherwise).  The inputs are left untouched.  One
+    World(n, ranks) loads the keys, sorts them unless assume_sorted says they
+    are sorted already (in that order; not checked), and searches every
+    non-empty rank, adding from the second on.  No keys: zeros."""
+    if side not in ("left", "right"):
+        raise ValueError(f"side {side!r}: not 'left' or 'right'")
+    return _search(keys, queries, side, descending, ranks, radix_bits, key_type, assume_sorted)
+
+
+def count_of(keys, queries, descending: bool = False, ranks: int = 1, radix_bits: int = 8,
+             key_type: Optional[int] = None, assume_sorted: bool = False):
+    """How often every query occurs among the keys of a device column: int64 of
+    the queries' length.  Keys are equal when their bits are.  Arguments as
+    searchsorted()."""
+    return _search(keys, queries, "count", descending, ranks, radix_bits, key_type, assume_sorted)
+
+
+def isin(queries, keys, descending: bool = False, ranks: int = 1, radix_bits: int = 8,
+         key_type: Optional[int] = None, assume_sorted: bool = False):
+    """Whether every query occurs among the keys of a device column: a bool
+    tensor of the queries' length, count_of(keys, queries) > 0 (note the
+    argument order, torch.isin's).  No keys: all False."""
+    return _search(keys, queries, "count", descending, ranks, radix_bits, key_type, assume_sorted) > 0
+
+
 def plan_select(n: int, P: int, count: int, below: np.ndarray, equal: np.ndarray) -> dict:
     """lsb_plan_select, the host planner of the select: below[r], equal[r] =
     rank r's records below and equal to the pivot, count = k + 1 wanted
@@ -1145,6 +1219,32 @@ class World:
         rounds, read = ctypes.c_int(), ctypes.c_int64()
         _check(_lib().lsb_get_last_select(self._h, ctypes.byref(rounds), ctypes.byref(read)), "lsb_get_last_select")
         return int(rounds.value), int(read.value)
+
+    def search(self, rank: int, queries, out, side: str = "left", add: bool = False, descending: bool = False,
+               key_type: Optional[int] = None) -> None:
+        """lsb_search: for every query, the records of `rank` (sorted) whose
+        key is below it (side="left"), not above it ("right") or equal to it
+        ("count"), in the mapped keys' order, into out (add=True: added to
+        it).  queries: a 1-D contiguous CUDA torch tensor read with the key
+        type and order the load was given; out: int64, the same length and
+        device, no byte shared with queries.  Local, no collective: the sum
+        over the ranks is the answer for the whole array."""
+        import torch
+        if side not in _SEARCH_SIDES:
+            raise ValueError(f"side {side!r}: not one of {sorted(_SEARCH_SIDES)}")
+        _check_column(queries, "queries")
+        kt = _key_type_of(queries, key_type)
+        _check_column(out, "out", queries.device)
+        if out.dtype != torch.int64:
+            raise ValueError("out: not int64")
+        if out.numel() != queries.numel():
+            raise ValueError("queries and out differ in length")
+        m = queries.numel()
+        torch.cuda.current_stream(queries.device).synchronize()
+        _check(_lib().lsb_search(self._h, rank, m, queries.data_ptr() if m else None, kt,
+                                 ORDER_DESCENDING if descending else 0,
+                                 _SEARCH_SIDES[side] | (SEARCH_ADD if add else 0), out.data_ptr() if m else None),
+               "lsb_search")
 
     def scatter_global(self, arr: np.ndarray) -> None:
         """Load a global array of n records into the block partition."""

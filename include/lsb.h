@@ -716,6 +716,72 @@ int  lsb_store_select(lsb_ctx_t* ctx, int rank, int64_t cap, void* keys_dev, int
                       void* vals_dev, int val_bytes, int64_t* count);
 int  lsb_get_last_select(lsb_ctx_t* ctx, int* rounds, int64_t* records_read);
 
+/* ---- searching the sorted records: lower and upper bound, match count ------ */
+/* A question about a second column against the sorted one: where would this
+ * key go, is it present, and how often (searchsorted, bucketize, isin; the
+ * probe side of a sort-merge join or a dictionary lookup).
+ * Take a local rank whose A is sorted by mapped key: after lsb_sort, or any A
+ * for which lsb_check_sorted holds.  queries_dev is a column of m typed keys
+ * on that rank's device, read with key_type and flags as lsb_load_columns
+ * reads its keys.  With e_i = lsb_key_encode(queries_dev[i], key_type, flags):
+ *   LSB_SEARCH_LOWER   c_i = the number of the rank's records with key <  e_i
+ *   LSB_SEARCH_UPPER   c_i = the number with key <= e_i
+ *   LSB_SEARCH_COUNT   c_i = the number with key == e_i (UPPER - LOWER, in one
+ *                      call and one kernel)
+ * out_dev[i] = c_i; with LSB_SEARCH_ADD or-ed into mode, out_dev[i] += c_i.
+ *
+ * Across ranks: the global array (rank 0's slots, then rank 1's, ...) is
+ * sorted, so the global lower bound of a query is the sum of the ranks' c_i,
+ * and the same holds for UPPER and COUNT.  That is the whole cross-rank story:
+ * a loopback caller calls once per local rank, with LSB_SEARCH_ADD from the
+ * second on; a one-rank-per-process caller whose ranks hold the same queries
+ * adds the ranks' columns with an all-reduce of its own.  The call is local,
+ * not collective, and needs no plan from another call.  Two early-outs make a
+ * rank that a query does not fall into cheap: a query not above the rank's
+ * first key gives LOWER 0, a query above its last key gives here(rank),
+ * neither with a probe of a tile (UPPER alike: below the first key 0, not
+ * below the last here(rank)).
+ *
+ * Order: equality and order are those of the mapped unsigned key.  -0.0 is
+ * below +0.0; NaNs sort at both ends by sign, and a NaN equals only its own
+ * bit pattern; LSB_ORDER_DESCENDING searches an array that was loaded
+ * descending.  This is deliberately not torch.searchsorted's or numpy's float
+ * behaviour (where -0.0 == +0.0 and every NaN sorts last).
+ *
+ * Edges: m == 0 returns LSB_OK and launches nothing.  On a rank that holds no
+ * record every c_i is 0: zeros are written without LSB_SEARCH_ADD, nothing is
+ * touched with it.
+ * Unsorted A is the caller's error and is not detected.  The result is then
+ * unspecified, but every c_i lies in [0, here(rank)], no record outside the
+ * rank's here(rank) slots is read and nothing outside out_dev[0, m) is
+ * written: the probe indices are bounded by construction, not by the data.
+ *
+ * The first search of a rank after a change of its A reads the key of every
+ * 4096th record into a table (8 bytes per 4096 records of scratch, allocated
+ * at the rank's first search and freed with the context; lsb_rank_footprint
+ * does not model it, as for the other scratch).  The table is kept until
+ * lsb_generate, lsb_generate_ex, lsb_copy_in, lsb_load_columns, lsb_sort,
+ * lsb_pass, lsb_label_runs or lsb_scan_runs is called.  lsb_select leaves A
+ * bit for bit and uses B only, so it keeps the table; so do the calls that
+ * only read A.  A query then costs a binary search of that table and at most
+ * 12 probes of one 4096-record tile.
+ *
+ * LSB_ERR_INVALID, before anything is launched: null context, bad rank,
+ * m < 0, unknown key type or flag bits, unknown mode bits, and with m > 0 a
+ * null pointer, the pointer checks of lsb_load_columns on both columns
+ * (aligned to the element, 8 bytes for out_dev; device memory of the rank's
+ * device; the range inside its allocation), or query and output ranges that
+ * share a byte.  LSB_ERR_STATE: an earlier sort left the context unusable (as
+ * lsb_sort).
+ * Streams as lsb_store_columns: the call waits for the rank's stream, runs on
+ * it and returns when the column is written. */
+#define LSB_SEARCH_LOWER 0
+#define LSB_SEARCH_UPPER 1
+#define LSB_SEARCH_COUNT 2
+#define LSB_SEARCH_ADD   4   /* or-ed into mode: out_dev[i] += c_i */
+int  lsb_search(lsb_ctx_t* ctx, int rank, int64_t m, const void* queries_dev,
+                int key_type, int flags, int mode, int64_t* out_dev);
+
 /* ---- the hot path ------------------------------------------------------- */
 /* == mySort(A, B): all 64/radix_bits passes; result in A.  Asynchronous
  * with respect to the host except for the per-pass count exchange when

@@ -24,6 +24,8 @@
 //   - the planner of the select (lsb_plan_select) for every k of random
 //     partitions against the stable sort of the whole array; its refusals;
 //     lsb_select / lsb_store_select with a null context and bad arguments;
+//   - lsb_search with a null context, with a bad mode and with every argument
+//     bad: refused before the columns are looked at;
 //   - k_onesweep's tile geometry where passes of different tile sizes meet
 //     (csrc/lsb_ostile.h): the look-back rows' fill decision replayed over
 //     random launch sequences (no launch can read a row of its own parity
@@ -571,6 +573,20 @@ static void select_cases(std::mt19937_64& rng) {
   CHECK(lsb_get_last_select(nullptr, nullptr, nullptr) == LSB_ERR_INVALID, "last_select: null ctx");
 }
 
+// lsb_search's refusals that come before any device call.
+static void search_cases() {
+  uint64_t q[4] = {0, 1, 2, 3};  // host memory: never reaches a device call with a null context
+  int64_t out[4] = {-5, -5, -5, -5};
+  for (int mode : {LSB_SEARCH_LOWER, LSB_SEARCH_UPPER, LSB_SEARCH_COUNT, LSB_SEARCH_COUNT | LSB_SEARCH_ADD})
+    CHECK(lsb_search(nullptr, 0, 4, q, LSB_KEY_U64, 0, mode, out) == LSB_ERR_INVALID, "search: null ctx");
+  for (int mode : {3, 7, 8, -1, 1 << 30})
+    CHECK(lsb_search(nullptr, 0, 4, q, LSB_KEY_U64, 0, mode, out) == LSB_ERR_INVALID, "search: bad mode");
+  CHECK(lsb_search(nullptr, 0, 0, nullptr, LSB_KEY_U64, 0, LSB_SEARCH_LOWER, nullptr) == LSB_ERR_INVALID,
+        "search: null ctx, m = 0");
+  CHECK(lsb_search(nullptr, -1, -1, nullptr, 6, 2, 3, nullptr) == LSB_ERR_INVALID, "search: all bad");
+  for (int i = 0; i < 4; ++i) CHECK(out[i] == -5 && q[i] == (uint64_t)i, "search: a refusal writes nothing");
+}
+
 static int noop_ag(void*, const void*, void*, size_t) { return 0; }
 static int noop_a2a(void*, const void*, const size_t*, const size_t*, void*, const size_t*,
                     const size_t*) { return 0; }
@@ -733,6 +749,7 @@ int main() {
   keyform_case(rng);
   runs_cases(rng);
   select_cases(rng);
+  search_cases();
   onesweep_tile_cases(rng);
   uint64_t col[4] = {0, 1, 2, 3};  // host memory: never reaches a device call with a null context
   CHECK(lsb_load_columns(nullptr, 0, 0, 4, col, LSB_KEY_U64, col, 8, 0) == LSB_ERR_INVALID, "load: null ctx");
