@@ -459,6 +459,34 @@ int gather_boundaries(lsb_ctx* c, std::vector<uint64_t>& bnd) {
   return LSB_OK;
 }
 
+int gather_words(lsb_ctx* c, size_t W, uint64_t* area, const std::function<const uint64_t*(const Rank&)>& src_of,
+                 std::vector<uint64_t>& out) {
+  const size_t P = (size_t)c->P;
+  out.assign(P * W, 0);
+  if (c->mode == Mode::kLoopback) {
+    for (Rank& r : c->ranks) {
+      const uint64_t* src = src_of(r);
+      if (!src) continue;
+      HIP_TRY(hipSetDevice(r.dev));
+      HIP_TRY(hipStreamSynchronize(r.stream));
+      HIP_TRY(hipMemcpy(&out[(size_t)r.rank * W], src, sizeof(uint64_t) * W, hipMemcpyDeviceToHost));
+    }
+    return LSB_OK;
+  }
+  Rank& r = c->ranks[0];
+  HIP_TRY(hipSetDevice(r.dev));
+  uint64_t* mine = area + (size_t)r.rank * W;
+  if (const uint64_t* src = src_of(r))
+    HIP_TRY(hipMemcpyAsync(mine, src, sizeof(uint64_t) * W, hipMemcpyDeviceToDevice, r.stream));
+  else
+    HIP_TRY(hipMemsetAsync(mine, 0, sizeof(uint64_t) * W, r.stream));
+  // Each rank contributes its own W words (in-place all-gather).
+  LSB_TRY(coll_allgather_u64(c, r, mine, area, W));
+  HIP_TRY(hipMemcpyAsync(out.data(), area, sizeof(uint64_t) * W * P, hipMemcpyDeviceToHost, r.stream));
+  HIP_TRY(hipStreamSynchronize(r.stream));
+  return LSB_OK;
+}
+
 int allreduce_min_i64(lsb_ctx* c, int64_t* v) {
   if (c->mode == Mode::kLoopback) return LSB_OK;
   if (c->mode == Mode::kOps)

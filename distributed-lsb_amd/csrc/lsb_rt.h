@@ -28,6 +28,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <new>
 #include <string>
 #include <vector>
@@ -420,8 +421,34 @@ int coll_alltoallv_u64(lsb_ctx* c, Rank& r, const uint64_t* send, const size_t* 
                        const size_t* sd, uint64_t* recv, const size_t* rc, const size_t* rd,
                        size_t bound, hipStream_t stream = nullptr);
 int gather_boundaries(lsb_ctx* c, std::vector<uint64_t>& bnd);
+// out[r * W ..] = rank r's W words on the host, read from the device pointer
+// src_of(rank) of the process that holds the rank; a null pointer gives zeros.
+// Loopback reads each rank's own once its stream is done; a one-rank-per-
+// process context all-gathers them in place through `area`, P * W words of
+// device memory on ranks[0] (not looked at in loopback).
+int gather_words(lsb_ctx* c, size_t W, uint64_t* area, const std::function<const uint64_t*(const Rank&)>& src_of,
+                 std::vector<uint64_t>& out);
 int allreduce_min_i64(lsb_ctx* c, int64_t* v);
 int gather_span(lsb_ctx* c, uint64_t* kor, uint64_t* knor);
+
+// ---- guarded launches ---------------------------------------------------------
+// A kernel that writes from a plan recounts what the plan counted and sets its
+// error word when A has changed since (lsb_tile.h's recount guard).  *h = the
+// word of r at err, once r's stream is done.
+inline int read_guard(Rank& r, const uint32_t* err, uint32_t* h) {
+  *h = 0;
+  HIP_TRY(hipMemcpyAsync(h, err, sizeof *h, hipMemcpyDeviceToHost, r.stream));
+  HIP_TRY(hipStreamSynchronize(r.stream));
+  return LSB_OK;
+}
+// The word zeroed, launch() (-> an LSB code) on r's stream, and the word read.
+// What a set word means is the caller's: its text, and the plan it drops.
+template <typename Launch>
+int guarded_launch(Rank& r, uint32_t* err, uint32_t* h, Launch&& launch) {
+  HIP_TRY(hipMemsetAsync(err, 0, sizeof(uint64_t), r.stream));
+  LSB_TRY(launch());
+  return read_guard(r, err, h);
+}
 
 // recv[s * count ..] = send of rank s, for every local rank (loopback: device
 // copies once every rank's stream is done; otherwise the collective).

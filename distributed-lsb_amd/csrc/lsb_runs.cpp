@@ -58,42 +58,39 @@ uint64_t* scan_in(const Rank& r) { return r.scan_buf + lsb::run_tiles(r.here); }
 uint64_t* scan_trail(const Rank& r) { return r.scan_buf + 2 * lsb::run_tiles(r.here); }
 uint32_t* scan_err(const Rank& r) { return reinterpret_cast<uint32_t*>(scan_trail(r) + 1); }
 
-// Every rank's trail word on the host, the way gather_leads moves the leads;
-// empty ranks give zeros.
-int gather_trails(lsb_ctx* c, std::vector<uint64_t>& trail) {
-  const int P = c->P;
-  trail.assign((size_t)P, 0);
-  if (c->mode == Mode::kLoopback) {
-    for (Rank& r : c->ranks) {
-      if (r.here == 0) continue;
-      HIP_TRY(hipSetDevice(r.dev));
-      HIP_TRY(hipStreamSynchronize(r.stream));
-      HIP_TRY(hipMemcpy(&trail[(size_t)r.rank], scan_trail(r), 8, hipMemcpyDeviceToHost));
-    }
-    return LSB_OK;
-  }
-  Rank& r = c->ranks[0];
-  HIP_TRY(hipSetDevice(r.dev));
-  uint64_t* d = r.gather;  // >= P entries
-  HIP_TRY(hipMemsetAsync(d, 0, sizeof(uint64_t) * P, r.stream));
-  if (r.here > 0) HIP_TRY(hipMemcpyAsync(d + r.rank, scan_trail(r), 8, hipMemcpyDeviceToDevice, r.stream));
-  LSB_TRY(coll_allgather_u64(c, r, d + r.rank, d, 1));
-  HIP_TRY(hipMemcpyAsync(trail.data(), d, sizeof(uint64_t) * P, hipMemcpyDeviceToHost, r.stream));
-  HIP_TRY(hipStreamSynchronize(r.stream));
-  return LSB_OK;
-}
+// The run kernels' error word (lsb_store_runs, lsb_store_reduce, lsb_label_runs).
+uint32_t* run_err(const Rank& r) { return reinterpret_cast<uint32_t*>(r.run_sum + 4); }
 
-// The OR of the local ranks' scan error words, after their streams are done.
-int scan_errors(lsb_ctx* c, uint32_t* any) {
+// The OR of the non-empty local ranks' error words, after their streams are done.
+template <typename ErrOf>
+int read_guards(lsb_ctx* c, ErrOf err_of, uint32_t* any) {
   *any = 0;
   for (Rank& r : c->ranks) {
     if (r.here == 0) continue;
     HIP_TRY(hipSetDevice(r.dev));
     uint32_t h = 0;
-    HIP_TRY(hipMemcpyAsync(&h, scan_err(r), sizeof h, hipMemcpyDeviceToHost, r.stream));
-    HIP_TRY(hipStreamSynchronize(r.stream));
+    LSB_TRY(read_guard(r, err_of(r), &h));
     *any |= h;
   }
+  return LSB_OK;
+}
+
+// lsb_label_runs' and lsb_scan_runs' work: every non-empty local rank's A -> B
+// by launch_of(rank) on its own stream, then every rank's error word; the
+// ranks swap only when none of them found A changed.
+template <typename ErrOf, typename LaunchOf>
+int ranks_a_to_b(lsb_ctx* c, const char* where, const char* text, ErrOf err_of, LaunchOf launch_of) {
+  for (Rank& r : c->ranks) {
+    if (r.here == 0) continue;
+    HIP_TRY(hipSetDevice(r.dev));
+    HIP_TRY(hipMemsetAsync(err_of(r), 0, sizeof(uint64_t), r.stream));
+    LSB_TRY(launch_of(r));
+  }
+  uint32_t any = 0;
+  LSB_TRY(read_guards(c, err_of, &any));
+  if (any) return fail(LSB_ERR_STATE, where, text);
+  for (Rank& r : c->ranks)
+    if (r.here > 0) std::swap(r.A, r.B);
   return LSB_OK;
 }
 
@@ -107,48 +104,13 @@ hipError_t launch_scan_write(lsb_ctx* c, Rank& r, int sink, void* out) {
                                     r.stream);
 }
 
-// lsb_scan_runs' work, as label_ranks: every non-empty local rank's A -> B on
-// its own stream, then every rank's error word; the ranks swap only when none
-// of them found A changed.
 int scan_ranks(lsb_ctx* c, int mode) {
-  for (Rank& r : c->ranks) {
-    if (r.here == 0) continue;
-    HIP_TRY(hipSetDevice(r.dev));
-    HIP_TRY(hipMemsetAsync(scan_err(r), 0, sizeof(uint64_t), r.stream));
-    HIP_TRY(launch_scan_write(c, r, mode == LSB_LABEL_KEEP ? lsb::kScanKeep : lsb::kScanByValue, r.B));
-  }
-  uint32_t any = 0;
-  LSB_TRY(scan_errors(c, &any));
-  if (any) return fail(LSB_ERR_STATE, "lsb_scan_runs", "A changed since lsb_count_runs: no rank was written");
-  for (Rank& r : c->ranks)
-    if (r.here > 0) std::swap(r.A, r.B);
-  return LSB_OK;
-}
-
-// Every rank's leading-run word on the host, the way gather_summaries moves
-// the summaries; ranks that reduced none (sent[r] == 0) give zeros.
-int gather_leads(lsb_ctx* c, const std::vector<char>& sent, std::vector<uint64_t>& lead) {
-  const int P = c->P;
-  lead.assign((size_t)P, 0);
-  if (c->mode == Mode::kLoopback) {
-    for (Rank& r : c->ranks) {
-      if (!sent[r.rank]) continue;
-      HIP_TRY(hipSetDevice(r.dev));
-      HIP_TRY(hipStreamSynchronize(r.stream));
-      HIP_TRY(hipMemcpy(&lead[(size_t)r.rank], r.run_part + lsb::kRunLeadParts, 8, hipMemcpyDeviceToHost));
-    }
-    return LSB_OK;
-  }
-  Rank& r = c->ranks[0];
-  HIP_TRY(hipSetDevice(r.dev));
-  uint64_t* d = r.gather;  // >= P entries
-  HIP_TRY(hipMemsetAsync(d, 0, sizeof(uint64_t) * P, r.stream));
-  if (sent[r.rank])
-    HIP_TRY(hipMemcpyAsync(d + r.rank, r.run_part + lsb::kRunLeadParts, 8, hipMemcpyDeviceToDevice, r.stream));
-  LSB_TRY(coll_allgather_u64(c, r, d + r.rank, d, 1));
-  HIP_TRY(hipMemcpyAsync(lead.data(), d, sizeof(uint64_t) * P, hipMemcpyDeviceToHost, r.stream));
-  HIP_TRY(hipStreamSynchronize(r.stream));
-  return LSB_OK;
+  const int sink = mode == LSB_LABEL_KEEP ? lsb::kScanKeep : lsb::kScanByValue;
+  return ranks_a_to_b(c, "lsb_scan_runs", "A changed since lsb_count_runs: no rank was written", scan_err,
+                      [&](Rank& r) -> int {
+                        HIP_TRY(launch_scan_write(c, r, sink, r.B));
+                        return LSB_OK;
+                      });
 }
 
 // Two outputs of cap elements (of ea and eb bytes) share a byte.
@@ -158,58 +120,29 @@ bool columns_overlap(const void* a, size_t ea, const void* b, size_t eb, int64_t
   return pa < pb + (uintptr_t)cap * eb && pb < pa + (uintptr_t)cap * ea;
 }
 
-// Every rank's four summary words on the host, the way gather_boundaries
-// moves its four: loopback reads each rank's own, a one-rank-per-process
-// context all-gathers them through r.gather.  Empty ranks give zeros.
+// The ranks' words of a plan on the host through r.gather (at least 4 P
+// words): the four summary words, the leading-run word of the ranks that
+// reduced one (sent[r] != 0), the scan's trail word.  Empty ranks give zeros.
 int gather_summaries(lsb_ctx* c, std::vector<uint64_t>& sum) {
-  const int P = c->P;
-  sum.assign((size_t)P * 4, 0);
-  if (c->mode == Mode::kLoopback) {
-    for (Rank& r : c->ranks) {
-      if (r.here == 0) continue;
-      HIP_TRY(hipSetDevice(r.dev));
-      HIP_TRY(hipStreamSynchronize(r.stream));
-      HIP_TRY(hipMemcpy(&sum[(size_t)r.rank * 4], r.run_sum, 32, hipMemcpyDeviceToHost));
-    }
-    return LSB_OK;
-  }
-  Rank& r = c->ranks[0];
-  HIP_TRY(hipSetDevice(r.dev));
-  uint64_t* d = r.gather;  // >= 4 * P entries
-  HIP_TRY(hipMemsetAsync(d, 0, sizeof(uint64_t) * 4 * P, r.stream));
-  if (r.here > 0)
-    HIP_TRY(hipMemcpyAsync(d + (size_t)r.rank * 4, r.run_sum, 32, hipMemcpyDeviceToDevice, r.stream));
-  LSB_TRY(coll_allgather_u64(c, r, d + (size_t)r.rank * 4, d, 4));
-  HIP_TRY(hipMemcpyAsync(sum.data(), d, sizeof(uint64_t) * 4 * P, hipMemcpyDeviceToHost, r.stream));
-  HIP_TRY(hipStreamSynchronize(r.stream));
-  return LSB_OK;
+  return gather_words(c, 4, c->ranks[0].gather, [](const Rank& r) { return r.here > 0 ? r.run_sum : nullptr; }, sum);
+}
+int gather_leads(lsb_ctx* c, const std::vector<char>& sent, std::vector<uint64_t>& lead) {
+  return gather_words(
+      c, 1, c->ranks[0].gather,
+      [&](const Rank& r) { return sent[r.rank] ? r.run_part + lsb::kRunLeadParts : nullptr; }, lead);
+}
+int gather_trails(lsb_ctx* c, std::vector<uint64_t>& trail) {
+  return gather_words(c, 1, c->ranks[0].gather, [](const Rank& r) { return r.here > 0 ? scan_trail(r) : nullptr; },
+                      trail);
 }
 
-// lsb_label_runs' work: every non-empty local rank's A -> B on its own
-// stream, then every rank's error word; the ranks swap only when none of
-// them found A changed.
 int label_ranks(lsb_ctx* c, int mode) {
-  for (Rank& r : c->ranks) {
-    if (r.here == 0) continue;
-    HIP_TRY(hipSetDevice(r.dev));
-    uint32_t* err = reinterpret_cast<uint32_t*>(r.run_sum + 4);
-    HIP_TRY(hipMemsetAsync(err, 0, sizeof(uint64_t), r.stream));
-    HIP_TRY(lsb::launch_run_label(r.A, r.B, r.here, c->run_base[r.rank], c->run_head0[r.rank], r.run_cnt,
-                                  r.run_tbase, mode, err, r.stream));
-  }
-  uint32_t any = 0;
-  for (Rank& r : c->ranks) {
-    if (r.here == 0) continue;
-    HIP_TRY(hipSetDevice(r.dev));
-    uint32_t h = 0;
-    HIP_TRY(hipMemcpyAsync(&h, r.run_sum + 4, sizeof h, hipMemcpyDeviceToHost, r.stream));
-    HIP_TRY(hipStreamSynchronize(r.stream));
-    any |= h;
-  }
-  if (any) return fail(LSB_ERR_STATE, "lsb_label_runs", "A changed since lsb_count_runs: no rank was labelled");
-  for (Rank& r : c->ranks)
-    if (r.here > 0) std::swap(r.A, r.B);
-  return LSB_OK;
+  return ranks_a_to_b(c, "lsb_label_runs", "A changed since lsb_count_runs: no rank was labelled", run_err,
+                      [&](Rank& r) -> int {
+                        HIP_TRY(lsb::launch_run_label(r.A, r.B, r.here, c->run_base[r.rank], c->run_head0[r.rank],
+                                                      r.run_cnt, r.run_tbase, mode, run_err(r), r.stream));
+                        return LSB_OK;
+                      });
 }
 
 }  // namespace
@@ -323,14 +256,13 @@ int lsb_store_runs(lsb_ctx_t* c, int rank, int64_t cap, void* keys_dev, int key_
       if (columns_overlap(out[i], elem[i], out[j], elem[j], cap))
         return fail(LSB_ERR_INVALID, where, "outputs overlap");
   HIP_TRY(hipStreamSynchronize(r->stream));
-  uint32_t* err = reinterpret_cast<uint32_t*>(r->run_sum + 4);
-  HIP_TRY(hipMemsetAsync(err, 0, sizeof(uint64_t), r->stream));
-  HIP_TRY(lsb::launch_run_write(r->A, r->here, (int64_t)r->rank * c->per, c->run_head0[rank], r->run_cnt,
-                                r->run_tbase, keys_dev, key_type, flags, starts_dev, counts_dev, firsts_dev,
-                                val_bytes, mine, c->run_end[rank], err, r->stream));
   uint32_t h = 0;
-  HIP_TRY(hipMemcpyAsync(&h, err, sizeof h, hipMemcpyDeviceToHost, r->stream));
-  HIP_TRY(hipStreamSynchronize(r->stream));
+  LSB_TRY(guarded_launch(*r, run_err(*r), &h, [&]() -> int {
+    HIP_TRY(lsb::launch_run_write(r->A, r->here, (int64_t)r->rank * c->per, c->run_head0[rank], r->run_cnt,
+                                  r->run_tbase, keys_dev, key_type, flags, starts_dev, counts_dev, firsts_dev,
+                                  val_bytes, mine, c->run_end[rank], run_err(*r), r->stream));
+    return LSB_OK;
+  }));
   if (h) {
     runs_invalidate(c);
     return fail(LSB_ERR_STATE, where, "A changed since lsb_count_runs: the outputs are unspecified");
@@ -428,14 +360,13 @@ int lsb_store_reduce(lsb_ctx_t* c, int rank, int64_t cap, void* out_dev, int64_t
   LSB_TRY(check_column(*r, out_dev, 8, cap, where));
   LSB_TRY(ensure_reduce_scratch(*r));
   HIP_TRY(hipStreamSynchronize(r->stream));
-  uint32_t* err = reinterpret_cast<uint32_t*>(r->run_sum + 4);
-  HIP_TRY(hipMemsetAsync(err, 0, sizeof(uint64_t), r->stream));
-  HIP_TRY(lsb::launch_run_reduce(r->A, r->here, c->run_head0[rank], r->run_cnt, r->run_tbase, c->reduce_op,
-                                 c->reduce_type, c->run_tail[rank], r->run_lead, static_cast<uint64_t*>(out_dev), mine,
-                                 err, r->stream));
   uint32_t h = 0;
-  HIP_TRY(hipMemcpyAsync(&h, err, sizeof h, hipMemcpyDeviceToHost, r->stream));
-  HIP_TRY(hipStreamSynchronize(r->stream));
+  LSB_TRY(guarded_launch(*r, run_err(*r), &h, [&]() -> int {
+    HIP_TRY(lsb::launch_run_reduce(r->A, r->here, c->run_head0[rank], r->run_cnt, r->run_tbase, c->reduce_op,
+                                   c->reduce_type, c->run_tail[rank], r->run_lead, static_cast<uint64_t*>(out_dev),
+                                   mine, run_err(*r), r->stream));
+    return LSB_OK;
+  }));
   if (h) {
     runs_invalidate(c);
     return fail(LSB_ERR_STATE, where, "A changed since lsb_count_runs: the outputs are unspecified");
@@ -502,7 +433,7 @@ int lsb_plan_scan(lsb_ctx_t* c, int op, int val_type) {
     // The gather comes first: a rank whose guard fired still takes part in the collective.
     LSB_TRY(gather_trails(c, trail));
     uint32_t any = 0;
-    LSB_TRY(scan_errors(c, &any));
+    LSB_TRY(read_guards(c, scan_err, &any));
     if (any) {
       runs_invalidate(c);
       return fail(LSB_ERR_STATE, where, "A changed since lsb_count_runs");
@@ -532,11 +463,11 @@ int lsb_store_scan(lsb_ctx_t* c, int rank, int64_t cap, void* out_dev, int64_t* 
   HIP_TRY(hipSetDevice(r->dev));
   LSB_TRY(check_column(*r, out_dev, 8, cap, where));
   HIP_TRY(hipStreamSynchronize(r->stream));
-  HIP_TRY(hipMemsetAsync(scan_err(*r), 0, sizeof(uint64_t), r->stream));
-  HIP_TRY(launch_scan_write(c, *r, lsb::kScanColumn, out_dev));
   uint32_t h = 0;
-  HIP_TRY(hipMemcpyAsync(&h, scan_err(*r), sizeof h, hipMemcpyDeviceToHost, r->stream));
-  HIP_TRY(hipStreamSynchronize(r->stream));
+  LSB_TRY(guarded_launch(*r, scan_err(*r), &h, [&]() -> int {
+    HIP_TRY(launch_scan_write(c, *r, lsb::kScanColumn, out_dev));
+    return LSB_OK;
+  }));
   if (h) {
     runs_invalidate(c);
     return fail(LSB_ERR_STATE, where, "A changed since lsb_count_runs: the output is unspecified");

@@ -29,28 +29,26 @@
 // every tile_open before k_run_scan_chain, every tile_in before k_run_scan_write.  No
 // floating-point atomics: the order of every addition is the code's.
 // Positions, bases and counts are 64-bit throughout.
+//
+// The kernels that read A share one tile skeleton.  lsb_tile.h holds the
+// workgroup's geometry, the scan of the (wave, item) cells that numbers a
+// tile's heads (tile_cells) and the recount guard (tile_recount): a tile whose
+// own count of its heads is not the count's tile_cnt sets *err and writes
+// nothing.  Here are the loads and head ballots (wave_heads), and for the
+// kernels that combine values the scan of a wave's items (wave_scan_items) and
+// the waves' hand-over through LDS (tile_hand_over).
+#include <type_traits>
+
 #include "lsb_kernels.h"
 #include "lsb_keyform.h"
+#include "lsb_tile.h"
 
 namespace lsb {
 
 namespace {
 
-constexpr int kRunBlock = 256;                    // 4 waves
-constexpr int kRunWaves = kRunBlock / 64;
-constexpr int kRunItems = kTile / kRunBlock;      // records per lane and tile
-constexpr int kRunWaveRecs = kTile / kRunWaves;   // a wave's adjacent records of a tile
-constexpr int kRunCells = kRunWaves * kRunItems;  // (wave, item) cells of a tile, in position order
 constexpr int kRunGridCap = 8192;
 constexpr int kRunScanBlock = 1024;
-static_assert(kRunCells == 64, "k_run_write scans the cells in one wave");
-
-__device__ __forceinline__ int run_lane() { return (int)(threadIdx.x & 63); }
-
-// Set bits of mask below this lane.
-__device__ __forceinline__ uint32_t run_mbcnt(uint64_t mask) {
-  return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
 
 // The previous lane's x by DPP wave_shr:1 (every lane active); lane 0 gets edge.
 __device__ __forceinline__ uint64_t prev_lane(uint64_t x, uint64_t edge) {
@@ -65,7 +63,7 @@ __device__ __forceinline__ uint64_t last_lane(uint64_t x) {
          (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, 63);
 }
 
-// One wave's kRunWaveRecs records from position wave0 on, lane-striped: item
+// One wave's kTileWaveRecs records from position wave0 on, lane-striped: item
 // j of lane l is position wave0 + 64 j + l, so every load instruction reads
 // 1 KiB of adjacent records in 16-byte accesses.  heads[j] = ballot of the
 // item's heads (positions >= here have none; position 0 is one exactly when
@@ -74,11 +72,11 @@ __device__ __forceinline__ uint64_t last_lane(uint64_t x) {
 // Every lane of the wave must call it.
 template <bool VALS>
 __device__ __forceinline__ void wave_heads(const Elem* __restrict__ A, int64_t here, int64_t wave0, bool head0,
-                                           uint64_t (&key)[kRunItems], uint64_t (&val)[kRunItems],
-                                           uint64_t (&heads)[kRunItems]) {
-  const int lane = run_lane();
+                                           uint64_t (&key)[kTileItems], uint64_t (&val)[kTileItems],
+                                           uint64_t (&heads)[kTileItems]) {
+  const int lane = tile_lane();
 #pragma unroll
-  for (int j = 0; j < kRunItems; ++j) {
+  for (int j = 0; j < kTileItems; ++j) {
     const int64_t i = wave0 + j * 64 + lane;
     ulonglong2 v = make_ulonglong2(0, 0);
     if (i < here) v = *reinterpret_cast<const ulonglong2*>(A + i);
@@ -91,7 +89,7 @@ __device__ __forceinline__ void wave_heads(const Elem* __restrict__ A, int64_t h
   uint64_t edge = 0;
   if (lane == 0 && wave0 > 0 && wave0 < here) edge = A[wave0 - 1].key;
 #pragma unroll
-  for (int j = 0; j < kRunItems; ++j) {
+  for (int j = 0; j < kTileItems; ++j) {
     const int64_t i = wave0 + j * 64 + lane;
     const uint64_t prev = prev_lane(key[j], edge);
     const bool head = i < here && (i == 0 ? head0 : key[j] != prev);
@@ -102,21 +100,21 @@ __device__ __forceinline__ void wave_heads(const Elem* __restrict__ A, int64_t h
 
 // tile_cnt[t] = heads of tile t (position 0 is never one); *lead = the
 // smallest head of the rank, when it is below the value *lead held.
-__global__ __launch_bounds__(kRunBlock) void k_run_count(const Elem* __restrict__ A, int64_t here, int64_t tiles,
+__global__ __launch_bounds__(kTileBlock) void k_run_count(const Elem* __restrict__ A, int64_t here, int64_t tiles,
                                                          uint32_t* __restrict__ tile_cnt,
                                                          unsigned long long* __restrict__ lead) {
-  __shared__ uint32_t s_cnt[kRunWaves], s_first[kRunWaves];
+  __shared__ uint32_t s_cnt[kTileWaves], s_first[kTileWaves];
   const int wave = (int)(threadIdx.x >> 6);
   for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    uint64_t key[kRunItems], val[kRunItems], heads[kRunItems];
-    wave_heads<false>(A, here, tile * kTile + (int64_t)wave * kRunWaveRecs, false, key, val, heads);
+    uint64_t key[kTileItems], val[kTileItems], heads[kTileItems];
+    wave_heads<false>(A, here, tile * kTile + (int64_t)wave * kTileWaveRecs, false, key, val, heads);
     uint32_t cnt = 0, first = kTile;  // the same in every lane
 #pragma unroll
-    for (int j = kRunItems - 1; j >= 0; --j) {
+    for (int j = kTileItems - 1; j >= 0; --j) {
       cnt += (uint32_t)__popcll(heads[j]);
-      if (heads[j]) first = (uint32_t)(wave * kRunWaveRecs + j * 64 + __builtin_ctzll(heads[j]));
+      if (heads[j]) first = (uint32_t)(wave * kTileWaveRecs + j * 64 + __builtin_ctzll(heads[j]));
     }
-    if (run_lane() == 0) {
+    if (tile_lane() == 0) {
       s_cnt[wave] = cnt;
       s_first[wave] = first;
     }
@@ -124,7 +122,7 @@ __global__ __launch_bounds__(kRunBlock) void k_run_count(const Elem* __restrict_
     if (threadIdx.x == 0) {
       uint32_t total = 0, f = kTile;
 #pragma unroll
-      for (int w = 0; w < kRunWaves; ++w) {
+      for (int w = 0; w < kTileWaves; ++w) {
         total += s_cnt[w];
         f = s_first[w] < f ? s_first[w] : f;
       }
@@ -180,50 +178,31 @@ __global__ __launch_bounds__(kRunScanBlock) void k_run_scan(const Elem* __restri
 // i writes keys[h], starts[h], firsts[h].  Within a tile a head's number is
 // the tile's base + the heads of the (wave, item) cells before its own (a
 // 64-entry scan in LDS) + the heads below its lane in its cell's ballot:
-// adjacent heads write adjacent elements.  The tile's own recount must equal
-// the count's tile_cnt; otherwise A has changed since, *err is set and the
-// tile writes nothing, so no index leaves [0, runs).
-__global__ __launch_bounds__(kRunBlock) void k_run_write(const Elem* __restrict__ A, int64_t here, int64_t tiles,
+// adjacent heads write adjacent elements.  The recount guards every store of
+// the tile, so no index leaves [0, runs).
+__global__ __launch_bounds__(kTileBlock) void k_run_write(const Elem* __restrict__ A, int64_t here, int64_t tiles,
                                                          int64_t gbase, uint32_t head0,
                                                          const uint32_t* __restrict__ tile_cnt,
                                                          const int64_t* __restrict__ tile_base, void* __restrict__ keys,
                                                          int key_type, int flags, int64_t* __restrict__ starts,
                                                          void* __restrict__ firsts, int val_bytes,
                                                          uint32_t* __restrict__ err) {
-  __shared__ uint32_t s_cell[kRunCells];
+  __shared__ uint32_t s_cell[kTileCells];
   __shared__ uint32_t s_total;
-  const int lane = run_lane(), wave = (int)(threadIdx.x >> 6);
+  const int lane = tile_lane(), wave = (int)(threadIdx.x >> 6);
   const KeyForm form = key_form(key_type, flags);
   const bool k32 = key_bytes(key_type) == 4;
   for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    uint64_t key[kRunItems], val[kRunItems], heads[kRunItems];
-    const int64_t wave0 = tile * kTile + (int64_t)wave * kRunWaveRecs;
+    uint64_t key[kTileItems], val[kTileItems], heads[kTileItems];
+    const int64_t wave0 = tile * kTile + (int64_t)wave * kTileWaveRecs;
     wave_heads<true>(A, here, wave0, head0 != 0, key, val, heads);
+    tile_cells(s_cell, &s_total, [&](int j) { return (uint32_t)__popcll(heads[j]); });
+    if (tile_recount(s_total, tile, head0, tile_cnt, err)) {
+      const int64_t out0 = tile_base[tile] + (int64_t)(head0 - tile_first(tile, head0));
 #pragma unroll
-    for (int j = 0; j < kRunItems; ++j)
-      if (lane == j) s_cell[wave * kRunItems + j] = (uint32_t)__popcll(heads[j]);
-    __syncthreads();
-    if (wave == 0) {  // cell counts -> exclusive prefixes, and their total
-      const uint32_t c = s_cell[lane];
-      uint32_t incl = c;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += o;
-      }
-      s_cell[lane] = incl - c;
-      if (lane == 63) s_total = incl;
-    }
-    __syncthreads();
-    const uint32_t first = tile == 0 ? head0 : 0u;  // position 0 is the plan's, not the count's
-    if (s_total - first != tile_cnt[tile]) {
-      if (threadIdx.x == 0) atomicOr(err, 1u);
-    } else {
-      const int64_t out0 = tile_base[tile] + (int64_t)(head0 - first);
-#pragma unroll
-      for (int j = 0; j < kRunItems; ++j) {
+      for (int j = 0; j < kTileItems; ++j) {
         if ((heads[j] >> lane) & 1) {
-          const int64_t h = out0 + s_cell[wave * kRunItems + j] + run_mbcnt(heads[j]);
+          const int64_t h = out0 + s_cell[wave * kTileItems + j] + tile_mbcnt(heads[j]);
           if (keys) {
             const uint64_t k = decode(key[j], form);
             if (k32) static_cast<uint32_t*>(keys)[h] = (uint32_t)k;
@@ -254,47 +233,29 @@ typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
 // whole, at the position it was loaded from: each store instruction writes
 // 1 KiB of adjacent records, like the loads.  Plain stores.
 // A and B are different buffers: a wave reads A[wave0 - 1], another wave's
-// record.  The recount guards every store of the tile, as in k_run_write.
+// record.  The recount guards every store of the tile.
 template <int MODE>
-__global__ __launch_bounds__(kRunBlock) void k_run_label(const Elem* __restrict__ A, Elem* __restrict__ B,
+__global__ __launch_bounds__(kTileBlock) void k_run_label(const Elem* __restrict__ A, Elem* __restrict__ B,
                                                          int64_t here, int64_t tiles, int64_t gid0, uint32_t head0,
                                                          const uint32_t* __restrict__ tile_cnt,
                                                          const int64_t* __restrict__ tile_base,
                                                          uint32_t* __restrict__ err) {
-  __shared__ uint32_t s_cell[kRunCells];
+  __shared__ uint32_t s_cell[kTileCells];
   __shared__ uint32_t s_total;
-  const int lane = run_lane(), wave = (int)(threadIdx.x >> 6);
+  const int lane = tile_lane(), wave = (int)(threadIdx.x >> 6);
   for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    uint64_t key[kRunItems], val[kRunItems], heads[kRunItems];
-    const int64_t wave0 = tile * kTile + (int64_t)wave * kRunWaveRecs;
+    uint64_t key[kTileItems], val[kTileItems], heads[kTileItems];
+    const int64_t wave0 = tile * kTile + (int64_t)wave * kTileWaveRecs;
     // kLabelKeep drops the old value, and still loads whole records (as k_run_count)
     wave_heads<MODE != kLabelKeep>(A, here, wave0, head0 != 0, key, val, heads);
-#pragma unroll
-    for (int j = 0; j < kRunItems; ++j)
-      if (lane == j) s_cell[wave * kRunItems + j] = (uint32_t)__popcll(heads[j]);
-    __syncthreads();
-    if (wave == 0) {  // cell counts -> exclusive prefixes, and their total
-      const uint32_t c = s_cell[lane];
-      uint32_t incl = c;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += o;
-      }
-      s_cell[lane] = incl - c;
-      if (lane == 63) s_total = incl;
-    }
-    __syncthreads();
-    const uint32_t first = tile == 0 ? head0 : 0u;  // position 0 is the plan's, not the count's
-    if (s_total - first != tile_cnt[tile]) {
-      if (threadIdx.x == 0) atomicOr(err, 1u);
-    } else {
+    tile_cells(s_cell, &s_total, [&](int j) { return (uint32_t)__popcll(heads[j]); });
+    if (tile_recount(s_total, tile, head0, tile_cnt, err)) {
       // the id of a record with no head of the tile at or below it
-      const int64_t id0 = gid0 + tile_base[tile] + (int64_t)(head0 - first) - 1;
+      const int64_t id0 = gid0 + tile_base[tile] + (int64_t)(head0 - tile_first(tile, head0)) - 1;
 #pragma unroll
-      for (int j = 0; j < kRunItems; ++j) {
+      for (int j = 0; j < kTileItems; ++j) {
         const int64_t i = wave0 + j * 64 + lane;
-        const uint32_t upto = s_cell[wave * kRunItems + j] + run_mbcnt(heads[j]) + (uint32_t)((heads[j] >> lane) & 1);
+        const uint32_t upto = s_cell[wave * kTileItems + j] + tile_mbcnt(heads[j]) + (uint32_t)((heads[j] >> lane) & 1);
         if (i < here) {
           const u64x2 rec = {MODE == kLabelKeep ? key[j] : val[j], (uint64_t)(id0 + upto)};
           if constexpr (LSB_LABEL_NT) __builtin_nontemporal_store(rec, reinterpret_cast<u64x2*>(B + i));
@@ -358,6 +319,66 @@ __device__ __forceinline__ uint64_t shfl_down64(uint64_t x, int off) {
          (uint32_t)__shfl_down((int)(uint32_t)x, off, 64);
 }
 
+// A wave's items after wave_heads, x[j] in the combine's working form:
+// x[j] becomes the segmented inclusive scan in position order from the wave's
+// first record on, within an item across the lanes (wave_seg_scan), between
+// the items by the value of lane 63.  Returns what the wave leaves open at its
+// end (its records since its last head, all of them without one; the same in
+// every lane), *cnt = its heads.
+template <int F>
+__device__ __forceinline__ uint64_t wave_scan_items(const uint64_t (&heads)[kTileItems], uint64_t (&x)[kTileItems],
+                                                    int lane, uint32_t* cnt) {
+  const uint64_t le = ~0ull >> (63 - lane);  // the lanes at or below this one
+  uint64_t carry = red_identity(F);
+  uint32_t c = 0;
+#pragma unroll
+  for (int j = 0; j < kTileItems; ++j) {
+    const uint64_t m = heads[j] & le;
+    // the lanes below this one that belong to its segment
+    const int reach = m ? lane - (63 - __builtin_clzll(m)) : lane;
+    uint64_t v = wave_seg_scan<F>(x[j], lane, reach);
+    if (m == 0) v = red<F>(carry, v);  // in front of the item's first head: the segment open at the item's start
+    carry = last_lane(v);
+    c += (uint32_t)__popcll(heads[j]);
+    x[j] = v;
+  }
+  *cnt = c;
+  return carry;
+}
+
+// The waves' hand-over through LDS (s_part, s_cnt: kTileWaves entries each):
+// every wave leaves its open part and its head count, and folds those of the
+// waves before it in wave order, a wave with a head starting anew.  Returns
+// what they leave open at this wave's first record; *before = their heads;
+// *open = the same fold over all the waves, the tile's records since its last
+// head; *total = the tile's heads.  One barrier inside; the caller puts another
+// before the next tile's call.
+template <int F>
+__device__ __forceinline__ uint64_t tile_hand_over(uint64_t part, uint32_t cnt, int lane, int wave, uint64_t* s_part,
+                                                   uint32_t* s_cnt, uint32_t* before, uint64_t* open,
+                                                   uint32_t* total) {
+  if (lane == 0) {
+    s_part[wave] = part;
+    s_cnt[wave] = cnt;
+  }
+  __syncthreads();
+  uint64_t acc = red_identity(F), cw = acc;
+  uint32_t t = 0, b = 0;
+#pragma unroll
+  for (int w = 0; w < kTileWaves; ++w) {
+    if (w == wave) {
+      cw = acc;
+      b = t;
+    }
+    acc = s_cnt[w] ? s_part[w] : red<F>(acc, s_part[w]);
+    t += s_cnt[w];
+  }
+  *before = b;
+  *open = acc;
+  *total = t;
+  return cw;
+}
+
 // out[h] = F over the values of the records from head h up to the next head
 // or the tile's end, h numbered as in k_run_write; tile_lead[t] = F over the
 // tile's records in front of its first head (the whole tile without one, the
@@ -366,86 +387,56 @@ __device__ __forceinline__ uint64_t shfl_down64(uint64_t x, int off) {
 // A segmented inclusive reduction in position order, keyed by the head
 // ballots: within an item across the lanes (wave_seg_scan, six DPP steps),
 // between a wave's items by the value of lane 63, between the four waves
-// through LDS.
+// through LDS (wave_scan_items, tile_hand_over).  The hand-over's head counts
+// number the heads as well: those of the waves before, then of the wave's
+// items before, then of the lanes below.
 // The last record of a segment (the next position is a head, or the tile or
 // the rank ends there) holds the segment's value and writes it: every out[h]
 // and every tile_lead[t] is written once, by one lane.  The recount guards
-// all of it, as in k_run_write.
+// all of it.
 template <int F>
-__global__ __launch_bounds__(kRunBlock) void k_run_reduce(const Elem* __restrict__ A, int64_t here, int64_t tiles,
+__global__ __launch_bounds__(kTileBlock) void k_run_reduce(const Elem* __restrict__ A, int64_t here, int64_t tiles,
                                                           uint32_t head0, const uint32_t* __restrict__ tile_cnt,
                                                           const int64_t* __restrict__ tile_base, int val_type,
                                                           uint64_t* __restrict__ out,
                                                           uint64_t* __restrict__ tile_lead,
                                                           uint32_t* __restrict__ err) {
-  __shared__ uint32_t s_cell[kRunCells];
-  __shared__ uint32_t s_total;
-  __shared__ uint64_t s_part[kRunWaves];                   // a wave's records since its last head
-  __shared__ uint32_t s_has[kRunWaves], s_first[kRunWaves];  // a wave has a head; its first record is one
-  const int lane = run_lane(), wave = (int)(threadIdx.x >> 6);
+  __shared__ uint64_t s_part[kTileWaves];
+  __shared__ uint32_t s_cnt[kTileWaves], s_first[kTileWaves];  // s_first: a wave's first record is a head
+  const int lane = tile_lane(), wave = (int)(threadIdx.x >> 6);
   const KeyForm form = key_form(val_type, 0);
   const uint64_t le = ~0ull >> (63 - lane);  // the lanes at or below this one
   for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    uint64_t key[kRunItems], x[kRunItems], heads[kRunItems];
-    const int64_t wave0 = tile * kTile + (int64_t)wave * kRunWaveRecs;
+    uint64_t key[kTileItems], x[kTileItems], heads[kTileItems];
+    const int64_t wave0 = tile * kTile + (int64_t)wave * kTileWaveRecs;
     wave_heads<true>(A, here, wave0, head0 != 0, key, x, heads);
-    uint64_t carry = red_identity(F), any = 0;
 #pragma unroll
-    for (int j = 0; j < kRunItems; ++j) {
-      uint64_t v = red_load(F, x[j], form);
-      const uint64_t m = heads[j] & le;
-      // the lanes below this one that belong to its segment
-      const int reach = m ? lane - (63 - __builtin_clzll(m)) : lane;
-      v = wave_seg_scan<F>(v, lane, reach);
-      if (m == 0) v = red<F>(carry, v);  // in front of the item's first head: the segment open at the item's start
-      carry = last_lane(v);
-      any |= heads[j];
-      x[j] = v;
-      if (lane == j) s_cell[wave * kRunItems + j] = (uint32_t)__popcll(heads[j]);
-    }
-    if (lane == 0) {
-      s_part[wave] = carry;
-      s_has[wave] = any != 0;
-      s_first[wave] = (uint32_t)(heads[0] & 1);
-    }
-    __syncthreads();
-    if (wave == 0) {  // cell counts -> exclusive prefixes, and their total
-      const uint32_t c = s_cell[lane];
-      uint32_t incl = c;
+    for (int j = 0; j < kTileItems; ++j) x[j] = red_load(F, x[j], form);
+    uint32_t cnt, before, total;
+    uint64_t open;
+    const uint64_t part = wave_scan_items<F>(heads, x, lane, &cnt);
+    if (lane == 0) s_first[wave] = (uint32_t)(heads[0] & 1);
+    // What the waves before this one leave open at its first record.
+    const uint64_t cw = tile_hand_over<F>(part, cnt, lane, wave, s_part, s_cnt, &before, &open, &total);
+    if (tile_recount(total, tile, head0, tile_cnt, err)) {
+      const int64_t out0 = tile_base[tile] + (int64_t)(head0 - tile_first(tile, head0));
+      const uint64_t after = wave + 1 < kTileWaves ? s_first[wave + 1] : 1;  // the tile ends after wave 3
+      uint32_t cell = before;  // the tile's heads in front of item j: the waves before, then this wave's items
 #pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += o;
-      }
-      s_cell[lane] = incl - c;
-      if (lane == 63) s_total = incl;
-    }
-    __syncthreads();
-    const uint32_t first = tile == 0 ? head0 : 0u;  // position 0 is the plan's, not the count's
-    if (s_total - first != tile_cnt[tile]) {
-      if (threadIdx.x == 0) atomicOr(err, 1u);
-    } else {
-      const int64_t out0 = tile_base[tile] + (int64_t)(head0 - first);
-      // What the waves before this one leave open at its first record.
-      uint64_t cw = red_identity(F);
-      for (int w = 0; w < wave; ++w) cw = s_has[w] ? s_part[w] : red<F>(cw, s_part[w]);
-      const uint64_t after = wave + 1 < kRunWaves ? s_first[wave + 1] : 1;  // the tile ends after wave 3
-      bool pre = true;  // no head of this wave in the items before j
-#pragma unroll
-      for (int j = 0; j < kRunItems; ++j) {
+      for (int j = 0; j < kTileItems; ++j) {
         const int64_t i = wave0 + j * 64 + lane;
-        const uint64_t nb = j + 1 < kRunItems ? heads[(j + 1) % kRunItems] & 1 : after;
+        const uint64_t nb = j + 1 < kTileItems ? heads[(j + 1) % kTileItems] & 1 : after;
         const uint64_t next = (heads[j] >> 1) | (nb << 63);  // the heads of the positions one up
         const uint64_t m = heads[j] & le;
         if (i < here && (((next >> lane) & 1) || i + 1 == here)) {
           uint64_t v = x[j];
-          if (pre && m == 0) v = red<F>(cw, v);
+          if (cell == before && m == 0) v = red<F>(cw, v);  // no head of this wave at or below the record
           v = red_store(F, v, form);
-          const uint32_t upto = s_cell[wave * kRunItems + j] + (uint32_t)__popcll(m);  // heads of the tile up to here
+          const uint32_t upto = cell + (uint32_t)__popcll(m);  // heads of the tile up to here
           if (upto) out[out0 + upto - 1] = v;
           else tile_lead[tile] = v;
         }
-        pre = pre && heads[j] == 0;
+        cell += (uint32_t)__popcll(heads[j]);
       }
       if (threadIdx.x == 0 && (heads[0] & 1)) tile_lead[tile] = red_store(F, red_identity(F), form);
     }
@@ -503,7 +494,7 @@ __global__ __launch_bounds__(kRunScanBlock) void k_run_carry(int64_t tiles, uint
 // The workgroup's F over every thread's acc, in an order the code fixes (a
 // tree over each wave's lanes, then the waves in order); thread 0 has it.
 __device__ __forceinline__ uint64_t block_red(int F, uint64_t acc, uint64_t* s_wave) {
-  const int lane = run_lane();
+  const int lane = tile_lane();
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     const uint64_t y = shfl_down64(acc, off);
@@ -511,33 +502,33 @@ __device__ __forceinline__ uint64_t block_red(int F, uint64_t acc, uint64_t* s_w
   }
   if (lane == 0) s_wave[threadIdx.x >> 6] = acc;
   __syncthreads();
-  for (int w = 1; w < kRunWaves; ++w) acc = red(F, acc, s_wave[w]);
+  for (int w = 1; w < kTileWaves; ++w) acc = red(F, acc, s_wave[w]);
   return acc;
 }
 
 // parts[b] = F over the values of workgroup b's tiles of A[0, lead), tile by
 // tile in a grid stride.
-__global__ __launch_bounds__(kRunBlock) void k_run_lead(const Elem* __restrict__ A, int64_t lead, int F, int val_type,
+__global__ __launch_bounds__(kTileBlock) void k_run_lead(const Elem* __restrict__ A, int64_t lead, int F, int val_type,
                                                         uint64_t* __restrict__ parts) {
-  __shared__ uint64_t s_wave[kRunWaves];
+  __shared__ uint64_t s_wave[kTileWaves];
   const KeyForm form = key_form(val_type, 0);
   uint64_t acc = red_identity(F);
   for (int64_t base = (int64_t)blockIdx.x * kTile; base < lead; base += (int64_t)gridDim.x * kTile)
-    for (int j = 0; j < kRunItems; ++j) {
-      const int64_t i = base + j * kRunBlock + threadIdx.x;
+    for (int j = 0; j < kTileItems; ++j) {
+      const int64_t i = base + j * kTileBlock + threadIdx.x;
       if (i < lead) acc = red(F, acc, red_load(F, A[i].val, form));
     }
   acc = block_red(F, acc, s_wave);
   if (threadIdx.x == 0) parts[blockIdx.x] = red_store(F, acc, form);
 }
 
-// One workgroup: *out = F over parts[0, cnt), thread t taking cnt / kRunBlock
+// One workgroup: *out = F over parts[0, cnt), thread t taking cnt / kTileBlock
 // (rounded up) adjacent ones in index order.
-__global__ __launch_bounds__(kRunBlock) void k_run_lead_sum(const uint64_t* __restrict__ parts, int cnt, int F,
+__global__ __launch_bounds__(kTileBlock) void k_run_lead_sum(const uint64_t* __restrict__ parts, int cnt, int F,
                                                             int val_type, uint64_t* __restrict__ out) {
-  __shared__ uint64_t s_wave[kRunWaves];
+  __shared__ uint64_t s_wave[kTileWaves];
   const KeyForm form = key_form(val_type, 0);
-  const int chunk = (cnt + kRunBlock - 1) / kRunBlock;
+  const int chunk = (cnt + kTileBlock - 1) / kTileBlock;
   uint64_t acc = red_identity(F);
   for (int i = (int)threadIdx.x * chunk; i < ((int)threadIdx.x + 1) * chunk && i < cnt; ++i)
     acc = red(F, acc, red_load(F, parts[i], form));
@@ -551,75 +542,15 @@ __global__ __launch_bounds__(kRunBlock) void k_run_lead_sum(const uint64_t* __re
 enum ScanKind { kSkAdd = kRedAdd, kSkFadd = kRedFadd, kSkMin = kRedMin, kSkMax = kRedMax, kSkCount = 4, kSkStart = 5 };
 constexpr int sk_form(int K) { return K >= kSkCount ? (int)kRedAdd : K; }
 
-// A wave's items after wave_heads, x[j] in the combine's working form:
-// x[j] becomes the segmented inclusive scan in position order from the wave's
-// first record on, within an item across the lanes (wave_seg_scan), between
-// the items by the value of lane 63: k_run_reduce's first loop.  Returns what
-// the wave leaves open at its end (its records since its last head, all of
-// them without one; the same in every lane), *cnt = its heads.
-template <int F>
-__device__ __forceinline__ uint64_t wave_scan_items(const uint64_t (&heads)[kRunItems], uint64_t (&x)[kRunItems],
-                                                    int lane, uint32_t* cnt) {
-  const uint64_t le = ~0ull >> (63 - lane);  // the lanes at or below this one
-  uint64_t carry = red_identity(F);
-  uint32_t c = 0;
-#pragma unroll
-  for (int j = 0; j < kRunItems; ++j) {
-    const uint64_t m = heads[j] & le;
-    // the lanes below this one that belong to its segment
-    const int reach = m ? lane - (63 - __builtin_clzll(m)) : lane;
-    uint64_t v = wave_seg_scan<F>(x[j], lane, reach);
-    if (m == 0) v = red<F>(carry, v);  // in front of the item's first head: the segment open at the item's start
-    carry = last_lane(v);
-    c += (uint32_t)__popcll(heads[j]);
-    x[j] = v;
-  }
-  *cnt = c;
-  return carry;
-}
-
-// The waves' hand-over through LDS (s_part, s_cnt: kRunWaves entries each):
-// every wave leaves its open part and its head count, and folds those of the
-// waves before it in wave order, a wave with a head starting anew.  Returns
-// what they leave open at this wave's first record; *before = their heads;
-// *open = the same fold over all the waves, the tile's records since its last
-// head; *total = the tile's heads.  One barrier inside; the caller puts another
-// before the next tile's call.
-template <int F>
-__device__ __forceinline__ uint64_t tile_hand_over(uint64_t part, uint32_t cnt, int lane, int wave, uint64_t* s_part,
-                                                   uint32_t* s_cnt, uint32_t* before, uint64_t* open,
-                                                   uint32_t* total) {
-  if (lane == 0) {
-    s_part[wave] = part;
-    s_cnt[wave] = cnt;
-  }
-  __syncthreads();
-  uint64_t acc = red_identity(F), cw = acc;
-  uint32_t t = 0, b = 0;
-#pragma unroll
-  for (int w = 0; w < kRunWaves; ++w) {
-    if (w == wave) {
-      cw = acc;
-      b = t;
-    }
-    acc = s_cnt[w] ? s_part[w] : red<F>(acc, s_part[w]);
-    t += s_cnt[w];
-  }
-  *before = b;
-  *open = acc;
-  *total = t;
-  return cw;
-}
-
 // The records' operands in the working form: the value (encoded for min and
 // max), 1 for the counting kinds, the identity past the rank's end, so that
 // the last tile's open part holds the rank's records only.
 template <int K>
-__device__ __forceinline__ void scan_operands(uint64_t (&x)[kRunItems], int64_t wave0, int64_t here, int lane,
+__device__ __forceinline__ void scan_operands(uint64_t (&x)[kTileItems], int64_t wave0, int64_t here, int lane,
                                               const KeyForm& form) {
   constexpr int F = sk_form(K);
 #pragma unroll
-  for (int j = 0; j < kRunItems; ++j) {
+  for (int j = 0; j < kTileItems; ++j) {
     const int64_t i = wave0 + j * 64 + lane;
     x[j] = i < here ? (K >= kSkCount ? 1ull : red_load(F, x[j], form)) : red_identity(F);
   }
@@ -627,30 +558,29 @@ __device__ __forceinline__ void scan_operands(uint64_t (&x)[kRunItems], int64_t 
 
 // tile_open[t] = the combine over tile t's records from its last head on, in
 // the working form (the whole tile without a head; position 0 is a head
-// exactly when head0).  The recount is k_run_reduce's: a tile whose heads are
-// not tile_cnt[t] sets *err.
+// exactly when head0).  A tile whose heads are not tile_cnt[t] sets *err
+// (tile_recount) and writes its tile_open all the same: the plan is dropped.
 template <int K>
-__global__ __launch_bounds__(kRunBlock) void k_run_scan_tile(const Elem* __restrict__ A, int64_t here, int64_t tiles,
+__global__ __launch_bounds__(kTileBlock) void k_run_scan_tile(const Elem* __restrict__ A, int64_t here, int64_t tiles,
                                                              uint32_t head0, const uint32_t* __restrict__ tile_cnt,
                                                              int val_type, uint64_t* __restrict__ tile_open,
                                                              uint32_t* __restrict__ err) {
   constexpr int F = sk_form(K);
-  __shared__ uint64_t s_part[kRunWaves];
-  __shared__ uint32_t s_cnt[kRunWaves];
-  const int lane = run_lane(), wave = (int)(threadIdx.x >> 6);
+  __shared__ uint64_t s_part[kTileWaves];
+  __shared__ uint32_t s_cnt[kTileWaves];
+  const int lane = tile_lane(), wave = (int)(threadIdx.x >> 6);
   const KeyForm form = key_form(val_type, 0);
   for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    uint64_t key[kRunItems], x[kRunItems], heads[kRunItems];
-    const int64_t wave0 = tile * kTile + (int64_t)wave * kRunWaveRecs;
+    uint64_t key[kTileItems], x[kTileItems], heads[kTileItems];
+    const int64_t wave0 = tile * kTile + (int64_t)wave * kTileWaveRecs;
     wave_heads<(K < kSkCount)>(A, here, wave0, head0 != 0, key, x, heads);
     scan_operands<K>(x, wave0, here, lane, form);
     uint32_t cnt, before, total;
     uint64_t open;
     const uint64_t part = wave_scan_items<F>(heads, x, lane, &cnt);
     tile_hand_over<F>(part, cnt, lane, wave, s_part, s_cnt, &before, &open, &total);
-    if (threadIdx.x == 0) {
-      const uint32_t first = tile == 0 ? head0 : 0u;  // position 0 is the plan's, not the count's
-      if (total - first != tile_cnt[tile]) atomicOr(err, 1u);
+    if (threadIdx.x == 0) {  // nothing to keep the other threads from: only the guard's word matters here
+      tile_recount(total, tile, head0, tile_cnt, err);
       tile_open[tile] = open;
     }
     __syncthreads();
@@ -721,41 +651,38 @@ __global__ __launch_bounds__(kRunScanBlock) void k_run_scan_chain(int64_t tiles,
 // c - 1 and kSkStart the record's global position - (c - 1).
 // Every store is at the position its record was loaded from: a store
 // instruction writes adjacent elements across the lanes, like the loads.  The
-// recount guards every store of the tile, as in k_run_write.
+// recount guards every store of the tile.
 template <int K, int SINK>
-__global__ __launch_bounds__(kRunBlock) void k_run_scan_write(const Elem* __restrict__ A, void* __restrict__ out,
+__global__ __launch_bounds__(kTileBlock) void k_run_scan_write(const Elem* __restrict__ A, void* __restrict__ out,
                                                               int64_t here, int64_t tiles, int64_t gbase,
                                                               uint32_t head0, int64_t lead,
                                                               const uint32_t* __restrict__ tile_cnt,
                                                               const uint64_t* __restrict__ tile_in, int val_type,
                                                               uint64_t carry_bits, uint32_t* __restrict__ err) {
   constexpr int F = sk_form(K);
-  __shared__ uint64_t s_part[kRunWaves];
-  __shared__ uint32_t s_cnt[kRunWaves];
-  const int lane = run_lane(), wave = (int)(threadIdx.x >> 6);
+  __shared__ uint64_t s_part[kTileWaves];
+  __shared__ uint32_t s_cnt[kTileWaves];
+  const int lane = tile_lane(), wave = (int)(threadIdx.x >> 6);
   const KeyForm form = key_form(val_type, 0);
   const uint64_t carry = red_load(F, carry_bits, form);
   const uint64_t le = ~0ull >> (63 - lane);  // the lanes at or below this one
   for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    uint64_t key[kRunItems], val[kRunItems], x[kRunItems], heads[kRunItems];
-    const int64_t wave0 = tile * kTile + (int64_t)wave * kRunWaveRecs;
+    uint64_t key[kTileItems], val[kTileItems], x[kTileItems], heads[kTileItems];
+    const int64_t wave0 = tile * kTile + (int64_t)wave * kTileWaveRecs;
     wave_heads<(K < kSkCount || SINK == kScanByValue)>(A, here, wave0, head0 != 0, key, val, heads);
 #pragma unroll
-    for (int j = 0; j < kRunItems; ++j) x[j] = val[j];
+    for (int j = 0; j < kTileItems; ++j) x[j] = val[j];
     scan_operands<K>(x, wave0, here, lane, form);
     uint32_t cnt, before, total;
     uint64_t open;
     const uint64_t part = wave_scan_items<F>(heads, x, lane, &cnt);
     const uint64_t cw = tile_hand_over<F>(part, cnt, lane, wave, s_part, s_cnt, &before, &open, &total);
-    const uint32_t first = tile == 0 ? head0 : 0u;  // position 0 is the plan's, not the count's
-    if (total - first != tile_cnt[tile]) {
-      if (threadIdx.x == 0) atomicOr(err, 1u);
-    } else {
+    if (tile_recount(total, tile, head0, tile_cnt, err)) {
       const uint64_t tin = tile_in[tile];
       const uint64_t tc = red<F>(carry, tin);
       bool pre = true;  // no head of this wave in the items before j
 #pragma unroll
-      for (int j = 0; j < kRunItems; ++j) {
+      for (int j = 0; j < kTileItems; ++j) {
         const int64_t i = wave0 + j * 64 + lane;
         uint64_t v = x[j];
         if (pre && (heads[j] & le) == 0) {  // no head of this wave at or below the record
@@ -781,24 +708,42 @@ __global__ __launch_bounds__(kRunBlock) void k_run_scan_write(const Elem* __rest
   }
 }
 
-template <int K>
-void launch_scan_write_kind(int sink, dim3 grid, hipStream_t s, const Elem* A, void* out, int64_t here, int64_t tiles,
-                            int64_t gbase, uint32_t head0, int64_t lead, const uint32_t* tile_cnt,
-                            const uint64_t* tile_in, int val_type, uint64_t carry, uint32_t* err) {
-  const dim3 block(kRunBlock);
-  if (sink == kScanColumn)
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_run_scan_write<K, kScanColumn>), grid, block, 0, s, A, out, here, tiles,
-                       gbase, head0, lead, tile_cnt, tile_in, val_type, carry, err);
-  else if (sink == kScanKeep)
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_run_scan_write<K, kScanKeep>), grid, block, 0, s, A, out, here, tiles, gbase,
-                       head0, lead, tile_cnt, tile_in, val_type, carry, err);
-  else
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_run_scan_write<K, kScanByValue>), grid, block, 0, s, A, out, here, tiles,
-                       gbase, head0, lead, tile_cnt, tile_in, val_type, carry, err);
-}
-
 int scan_kind(int op, int val_type) {
   return op == kScanCount ? (int)kSkCount : op == kScanStart ? (int)kSkStart : red_form(op, val_type);
+}
+
+// f(std::integral_constant<int, V>()) for the run-time value V of a template
+// argument, so that a launch is written once: the reduce form, the scan kind,
+// the scan's sink.
+template <int V>
+using Const = std::integral_constant<int, V>;
+
+template <typename Fn>
+void with_red_form(int F, Fn&& f) {
+  switch (F) {
+    case kRedAdd: return f(Const<kRedAdd>());
+    case kRedFadd: return f(Const<kRedFadd>());
+    case kRedMin: return f(Const<kRedMin>());
+    default: return f(Const<kRedMax>());
+  }
+}
+
+template <typename Fn>
+void with_scan_kind(int K, Fn&& f) {
+  switch (K) {
+    case kSkCount: return f(Const<kSkCount>());
+    case kSkStart: return f(Const<kSkStart>());
+    default: return with_red_form(K, f);  // the four combines are the reduce forms
+  }
+}
+
+template <typename Fn>
+void with_scan_sink(int sink, Fn&& f) {
+  switch (sink) {
+    case kScanColumn: return f(Const<kScanColumn>());
+    case kScanKeep: return f(Const<kScanKeep>());
+    default: return f(Const<kScanByValue>());
+  }
 }
 
 int run_grid(int64_t work, int block) {
@@ -814,7 +759,7 @@ hipError_t launch_run_count(const Elem* A, int64_t here, uint32_t* tile_cnt, int
   const int64_t tiles = run_tiles(here);
   hipError_t e = hipMemsetAsync(sum + 3, 0xff, sizeof(uint64_t), s);  // lead: no head seen
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_run_count, dim3(run_grid(tiles, 1)), dim3(kRunBlock), 0, s, A, here, tiles, tile_cnt,
+  hipLaunchKernelGGL(k_run_count, dim3(run_grid(tiles, 1)), dim3(kTileBlock), 0, s, A, here, tiles, tile_cnt,
                      reinterpret_cast<unsigned long long*>(sum + 3));
   hipLaunchKernelGGL(k_run_scan, dim3(1), dim3(kRunScanBlock), 0, s, A, here, tiles, tile_cnt, tile_base, sum);
   return hipGetLastError();
@@ -830,7 +775,7 @@ hipError_t launch_run_write(const Elem* A, int64_t here, int64_t gbase, int head
     return hipErrorInvalidValue;
   if (here <= 0 || runs <= 0) return hipSuccess;
   const int64_t tiles = run_tiles(here);
-  hipLaunchKernelGGL(k_run_write, dim3(run_grid(tiles, 1)), dim3(kRunBlock), 0, s, A, here, tiles, gbase,
+  hipLaunchKernelGGL(k_run_write, dim3(run_grid(tiles, 1)), dim3(kTileBlock), 0, s, A, here, tiles, gbase,
                      (uint32_t)head0, tile_cnt, tile_base, keys, key_type, flags, starts, firsts, val_bytes, err);
   if (counts)
     hipLaunchKernelGGL(k_run_diff, dim3(run_grid(runs, 256)), dim3(256), 0, s, starts, counts, runs, end);
@@ -844,7 +789,7 @@ hipError_t launch_run_label(const Elem* A, Elem* B, int64_t here, int64_t gid0, 
     return hipErrorInvalidValue;
   if (here <= 0) return hipSuccess;
   const int64_t tiles = run_tiles(here);
-  const dim3 grid(run_grid(tiles, 1)), block(kRunBlock);
+  const dim3 grid(run_grid(tiles, 1)), block(kTileBlock);
   if (mode == kLabelKeep)
     hipLaunchKernelGGL(k_run_label<kLabelKeep>, grid, block, 0, s, A, B, here, tiles, gid0, (uint32_t)head0, tile_cnt,
                        tile_base, err);
@@ -859,8 +804,8 @@ hipError_t launch_run_lead(const Elem* A, int64_t lead, int op, int val_type, ui
   if (!reduce_valid(op, val_type) || lead <= 0 || !A || !parts || !out) return hipErrorInvalidValue;
   const int F = red_form(op, val_type);
   const int grid = run_grid(run_tiles(lead), 1);
-  hipLaunchKernelGGL(k_run_lead, dim3(grid), dim3(kRunBlock), 0, s, A, lead, F, val_type, parts);
-  hipLaunchKernelGGL(k_run_lead_sum, dim3(1), dim3(kRunBlock), 0, s, parts, grid, F, val_type, out);
+  hipLaunchKernelGGL(k_run_lead, dim3(grid), dim3(kTileBlock), 0, s, A, lead, F, val_type, parts);
+  hipLaunchKernelGGL(k_run_lead_sum, dim3(1), dim3(kTileBlock), 0, s, parts, grid, F, val_type, out);
   return hipGetLastError();
 }
 
@@ -872,25 +817,11 @@ hipError_t launch_run_reduce(const Elem* A, int64_t here, int head0, const uint3
     return hipErrorInvalidValue;
   const int64_t tiles = run_tiles(here);
   const int F = red_form(op, val_type);
-  const dim3 grid(run_grid(tiles, 1)), block(kRunBlock);
-  switch (F) {
-    case kRedAdd:
-      hipLaunchKernelGGL(k_run_reduce<kRedAdd>, grid, block, 0, s, A, here, tiles, (uint32_t)head0, tile_cnt,
-                         tile_base, val_type, out, tile_lead, err);
-      break;
-    case kRedFadd:
-      hipLaunchKernelGGL(k_run_reduce<kRedFadd>, grid, block, 0, s, A, here, tiles, (uint32_t)head0, tile_cnt,
-                         tile_base, val_type, out, tile_lead, err);
-      break;
-    case kRedMin:
-      hipLaunchKernelGGL(k_run_reduce<kRedMin>, grid, block, 0, s, A, here, tiles, (uint32_t)head0, tile_cnt,
-                         tile_base, val_type, out, tile_lead, err);
-      break;
-    default:
-      hipLaunchKernelGGL(k_run_reduce<kRedMax>, grid, block, 0, s, A, here, tiles, (uint32_t)head0, tile_cnt,
-                         tile_base, val_type, out, tile_lead, err);
-      break;
-  }
+  const dim3 grid(run_grid(tiles, 1)), block(kTileBlock);
+  with_red_form(F, [&](auto f) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_run_reduce<decltype(f)::value>), grid, block, 0, s, A, here, tiles,
+                       (uint32_t)head0, tile_cnt, tile_base, val_type, out, tile_lead, err);
+  });
   hipLaunchKernelGGL(k_run_carry, dim3(1), dim3(kRunScanBlock), 0, s, tiles, (uint32_t)head0, tile_cnt, tile_base,
                      tile_lead, F, val_type, tail, out);
   return hipGetLastError();
@@ -903,29 +834,12 @@ hipError_t launch_run_scan_plan(const Elem* A, int64_t here, int head0, const ui
       !tile_in || !trail || !err)
     return hipErrorInvalidValue;
   const int64_t tiles = run_tiles(here);
-  const dim3 grid(run_grid(tiles, 1)), block(kRunBlock);
-  switch (scan_kind(op, val_type)) {
-    case kSkAdd:
-      hipLaunchKernelGGL(k_run_scan_tile<kSkAdd>, grid, block, 0, s, A, here, tiles, (uint32_t)head0, tile_cnt,
-                         val_type, tile_open, err);
-      break;
-    case kSkFadd:
-      hipLaunchKernelGGL(k_run_scan_tile<kSkFadd>, grid, block, 0, s, A, here, tiles, (uint32_t)head0, tile_cnt,
-                         val_type, tile_open, err);
-      break;
-    case kSkMin:
-      hipLaunchKernelGGL(k_run_scan_tile<kSkMin>, grid, block, 0, s, A, here, tiles, (uint32_t)head0, tile_cnt,
-                         val_type, tile_open, err);
-      break;
-    case kSkMax:
-      hipLaunchKernelGGL(k_run_scan_tile<kSkMax>, grid, block, 0, s, A, here, tiles, (uint32_t)head0, tile_cnt,
-                         val_type, tile_open, err);
-      break;
-    default:  // both counting kinds scan ones
-      hipLaunchKernelGGL(k_run_scan_tile<kSkCount>, grid, block, 0, s, A, here, tiles, (uint32_t)head0, tile_cnt,
-                         val_type, tile_open, err);
-      break;
-  }
+  const dim3 grid(run_grid(tiles, 1)), block(kTileBlock);
+  with_scan_kind(scan_kind(op, val_type), [&](auto k) {
+    constexpr int K = decltype(k)::value == kSkStart ? (int)kSkCount : decltype(k)::value;  // both counting kinds scan ones
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_run_scan_tile<K>), grid, block, 0, s, A, here, tiles, (uint32_t)head0,
+                       tile_cnt, val_type, tile_open, err);
+  });
   hipLaunchKernelGGL(k_run_scan_chain, dim3(1), dim3(kRunScanBlock), 0, s, tiles, (uint32_t)head0, tile_cnt,
                      tile_open, scan_form(op, val_type), val_type, tile_in, trail);
   return hipGetLastError();
@@ -940,34 +854,13 @@ hipError_t launch_run_scan_write(const Elem* A, int64_t here, int64_t gbase, int
     return hipErrorInvalidValue;
   if (here <= 0) return hipSuccess;
   const int64_t tiles = run_tiles(here);
-  const dim3 grid(run_grid(tiles, 1));
-  const uint32_t h0 = (uint32_t)head0;
-  switch (scan_kind(op, val_type)) {
-    case kSkAdd:
-      launch_scan_write_kind<kSkAdd>(sink, grid, s, A, out, here, tiles, gbase, h0, lead, tile_cnt, tile_in, val_type,
-                                     carry, err);
-      break;
-    case kSkFadd:
-      launch_scan_write_kind<kSkFadd>(sink, grid, s, A, out, here, tiles, gbase, h0, lead, tile_cnt, tile_in, val_type,
-                                      carry, err);
-      break;
-    case kSkMin:
-      launch_scan_write_kind<kSkMin>(sink, grid, s, A, out, here, tiles, gbase, h0, lead, tile_cnt, tile_in, val_type,
-                                     carry, err);
-      break;
-    case kSkMax:
-      launch_scan_write_kind<kSkMax>(sink, grid, s, A, out, here, tiles, gbase, h0, lead, tile_cnt, tile_in, val_type,
-                                     carry, err);
-      break;
-    case kSkCount:
-      launch_scan_write_kind<kSkCount>(sink, grid, s, A, out, here, tiles, gbase, h0, lead, tile_cnt, tile_in,
-                                       val_type, carry, err);
-      break;
-    default:
-      launch_scan_write_kind<kSkStart>(sink, grid, s, A, out, here, tiles, gbase, h0, lead, tile_cnt, tile_in,
-                                       val_type, carry, err);
-      break;
-  }
+  const dim3 grid(run_grid(tiles, 1)), block(kTileBlock);
+  with_scan_kind(scan_kind(op, val_type), [&](auto k) {
+    with_scan_sink(sink, [&](auto snk) {
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_run_scan_write<decltype(k)::value, decltype(snk)::value>), grid, block, 0,
+                         s, A, out, here, tiles, gbase, (uint32_t)head0, lead, tile_cnt, tile_in, val_type, carry, err);
+    });
+  });
   return hipGetLastError();
 }
 

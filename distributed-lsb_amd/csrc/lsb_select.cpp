@@ -27,35 +27,12 @@ int ensure_store_scratch(Rank& r) {
   return LSB_OK;
 }
 
-// Every rank's table of the round on the host, the way gather_summaries moves
-// the run summaries: loopback reads each rank's own, a one-rank-per-process
-// context all-gathers them through its own gather area (r.gather may be
-// smaller).  Ranks that launched nothing (ran[r] == 0) give zeros.
+// Every rank's table of the round on the host, through the select's own
+// gather area (r.gather may be smaller).  Ranks that launched nothing
+// (ran[r] == 0) give zeros.
 int gather_tables(lsb_ctx* c, const std::vector<char>& ran, std::vector<uint64_t>& tab) {
-  const int P = c->P;
-  tab.assign((size_t)P * kSelWords, 0);
-  if (c->mode == Mode::kLoopback) {
-    for (Rank& r : c->ranks) {
-      if (!ran[r.rank]) continue;
-      HIP_TRY(hipSetDevice(r.dev));
-      HIP_TRY(hipStreamSynchronize(r.stream));
-      HIP_TRY(hipMemcpy(&tab[(size_t)r.rank * kSelWords], r.sel_buf, sizeof(uint64_t) * kSelWords,
-                        hipMemcpyDeviceToHost));
-    }
-    return LSB_OK;
-  }
-  Rank& r = c->ranks[0];
-  HIP_TRY(hipSetDevice(r.dev));
-  uint64_t* d = r.sel_gather;
-  uint64_t* mine = d + (size_t)r.rank * kSelWords;
-  if (ran[r.rank])
-    HIP_TRY(hipMemcpyAsync(mine, r.sel_buf, sizeof(uint64_t) * kSelWords, hipMemcpyDeviceToDevice, r.stream));
-  else
-    HIP_TRY(hipMemsetAsync(mine, 0, sizeof(uint64_t) * kSelWords, r.stream));
-  LSB_TRY(coll_allgather_u64(c, r, mine, d, kSelWords));
-  HIP_TRY(hipMemcpyAsync(tab.data(), d, sizeof(uint64_t) * kSelWords * P, hipMemcpyDeviceToHost, r.stream));
-  HIP_TRY(hipStreamSynchronize(r.stream));
-  return LSB_OK;
+  return gather_words(c, kSelWords, c->ranks[0].sel_gather,
+                      [&](const Rank& r) { return ran[r.rank] ? r.sel_buf : nullptr; }, tab);
 }
 
 // Where a rank's candidates are read from in the next round.
@@ -240,15 +217,15 @@ int lsb_store_select(lsb_ctx_t* c, int rank, int64_t cap, void* keys_dev, int ke
   LSB_TRY(ensure_store_scratch(*r));
   HIP_TRY(hipStreamSynchronize(r->stream));
   uint32_t* err = reinterpret_cast<uint32_t*>(r->sel_buf + kSelWords);
-  HIP_TRY(hipMemsetAsync(err, 0, sizeof(uint64_t), r->stream));
   const int64_t lt = c->sel_below[rank];
-  HIP_TRY(lsb::launch_select_count(r->A, r->here, c->sel_pivot, lt, c->sel_equal[rank], r->sel_cnt, r->sel_tbase, err,
-                                   r->stream));
-  HIP_TRY(lsb::launch_select_write(r->A, r->here, c->sel_pivot, mine - lt, mine, r->sel_cnt, r->sel_tbase, keys_dev,
-                                   key_type, flags, vals_dev, val_bytes, err, r->stream));
   uint32_t h = 0;
-  HIP_TRY(hipMemcpyAsync(&h, err, sizeof h, hipMemcpyDeviceToHost, r->stream));
-  HIP_TRY(hipStreamSynchronize(r->stream));
+  LSB_TRY(guarded_launch(*r, err, &h, [&]() -> int {
+    HIP_TRY(lsb::launch_select_count(r->A, r->here, c->sel_pivot, lt, c->sel_equal[rank], r->sel_cnt, r->sel_tbase,
+                                     err, r->stream));
+    HIP_TRY(lsb::launch_select_write(r->A, r->here, c->sel_pivot, mine - lt, mine, r->sel_cnt, r->sel_tbase, keys_dev,
+                                     key_type, flags, vals_dev, val_bytes, err, r->stream));
+    return LSB_OK;
+  }));
   if (h) {
     select_invalidate(c);
     return fail(LSB_ERR_STATE, where, "A changed since lsb_select: the outputs are unspecified");

@@ -13,33 +13,23 @@
 // No workgroup waits for another: a round's counts go to the host between two
 // launches, a tile's base is ready before k_sel_write starts.  Positions,
 // bases and counts are 64-bit throughout.
+// The workgroup's geometry and the scan of a tile's (wave, item) cells are
+// lsb_tile.h's, shared with lsb_runs.hip.
 #include "lsb_kernels.h"
 #include "lsb_keyform.h"
+#include "lsb_tile.h"
 
 namespace lsb {
 
 namespace {
 
-constexpr int kSelBlock = 256;                    // 4 waves
-constexpr int kSelWaves = kSelBlock / 64;
-constexpr int kSelItems = kTile / kSelBlock;      // records per lane and tile
-constexpr int kSelWaveRecs = kTile / kSelWaves;   // a wave's adjacent records of a tile (k_sel_count, k_sel_write)
-constexpr int kSelCells = kSelWaves * kSelItems;  // (wave, item) cells of a tile, in position order
-constexpr int kSelGridCap = 2048;                 // 8 workgroups per CU; the tiles beyond are strided over
+constexpr int kSelGridCap = 2048;   // 8 workgroups per CU; the tiles beyond are strided over
 constexpr int kSelScanBlock = 1024;
-constexpr int kSelStage = 512;                    // records a wave stages in LDS per reservation in dst
-static_assert(kSelCells == 64, "k_sel_write scans the cells in one wave");
+constexpr int kSelStage = 512;      // records a wave stages in LDS per reservation in dst
 static_assert(kTile < (1 << 16), "a tile's two counts share one 32-bit word");
 
 typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ int sel_lane() { return (int)(threadIdx.x & 63); }
-
-// Set bits of mask below this lane.
-__device__ __forceinline__ uint32_t sel_mbcnt(uint64_t mask) {
-  return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
 
 __device__ __forceinline__ uint64_t first_lane(uint64_t x) {
   return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(x >> 32)) << 32) |
@@ -60,19 +50,19 @@ __device__ __forceinline__ uint64_t first_lane(uint64_t x) {
 // records, from the round before: a slot at or past it is not stored and sets
 // words[kSelHist + 1].
 template <bool SPAN, bool COMPACT>
-__global__ __launch_bounds__(kSelBlock) void k_sel_hist(const Elem* __restrict__ src, int64_t m, int64_t tiles,
+__global__ __launch_bounds__(kTileBlock) void k_sel_hist(const Elem* __restrict__ src, int64_t m, int64_t tiles,
                                                         int shift, uint64_t prefix, uint64_t mask,
                                                         Elem* __restrict__ dst, int64_t bound,
                                                         unsigned long long* __restrict__ words) {
-  __shared__ uint32_t hist[kSelWaves][kSelHist];
-  __shared__ uint64_t span_or[kSelWaves], span_nor[kSelWaves];
-  __shared__ u64x2 stage[COMPACT ? kSelWaves * kSelStage : 1];
-  const int lane = sel_lane(), w = (int)(threadIdx.x >> 6);
+  __shared__ uint32_t hist[kTileWaves][kSelHist];
+  __shared__ uint64_t span_or[kTileWaves], span_nor[kTileWaves];
+  __shared__ u64x2 stage[COMPACT ? kTileWaves * kSelStage : 1];
+  const int lane = tile_lane(), w = (int)(threadIdx.x >> 6);
   const uint64_t* __restrict__ keys = reinterpret_cast<const uint64_t*>(src);
   u64x2* const mine = stage + (COMPACT ? w * kSelStage : 0);
   uint64_t kor = 0, knor = 0;
   uint32_t fill = 0;  // staged records of this wave: the same in every lane
-  for (int i = threadIdx.x; i < kSelWaves * kSelHist; i += kSelBlock) (&hist[0][0])[i] = 0;
+  for (int i = threadIdx.x; i < kTileWaves * kSelHist; i += kTileBlock) (&hist[0][0])[i] = 0;
   __syncthreads();
 
   // The wave's staged records into dst, at the slots it reserves for them.
@@ -93,15 +83,15 @@ __global__ __launch_bounds__(kSelBlock) void k_sel_hist(const Elem* __restrict__
 
   for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
     const int64_t tb = tile * kTile;
-    uint64_t k[kSelItems];
+    uint64_t k[kTileItems];
 #pragma unroll
-    for (int i = 0; i < kSelItems; ++i) {
-      const int64_t idx = tb + (int64_t)i * kSelBlock + threadIdx.x;
+    for (int i = 0; i < kTileItems; ++i) {
+      const int64_t idx = tb + (int64_t)i * kTileBlock + threadIdx.x;
       k[i] = idx < m ? __builtin_nontemporal_load(keys + 2 * idx) : 0ull;  // streaming
     }
 #pragma unroll
-    for (int i = 0; i < kSelItems; ++i) {
-      const int64_t idx = tb + (int64_t)i * kSelBlock + threadIdx.x;
+    for (int i = 0; i < kTileItems; ++i) {
+      const int64_t idx = tb + (int64_t)i * kTileBlock + threadIdx.x;
       const bool valid = idx < m;
       if (SPAN && valid) {
         kor |= k[i];
@@ -120,7 +110,7 @@ __global__ __launch_bounds__(kSelBlock) void k_sel_hist(const Elem* __restrict__
         if (hits) {  // the same in every lane
           const uint32_t cnt = (uint32_t)__popcll(hits);
           if (fill + cnt > (uint32_t)kSelStage) flush();
-          if (match) mine[fill + sel_mbcnt(hits)] = u64x2{k[i], src[idx].val};
+          if (match) mine[fill + tile_mbcnt(hits)] = u64x2{k[i], src[idx].val};
           fill += cnt;
         }
       }
@@ -131,10 +121,10 @@ __global__ __launch_bounds__(kSelBlock) void k_sel_hist(const Elem* __restrict__
     if (fill) flush();
   }
   __syncthreads();
-  for (int b = threadIdx.x; b < kSelHist; b += kSelBlock) {
+  for (int b = threadIdx.x; b < kSelHist; b += kTileBlock) {
     uint64_t s = 0;
 #pragma unroll
-    for (int ww = 0; ww < kSelWaves; ++ww) s += hist[ww][b];
+    for (int ww = 0; ww < kTileWaves; ++ww) s += hist[ww][b];
     if (s) atomicAdd(&words[b], (unsigned long long)s);
   }
   if constexpr (SPAN) {
@@ -151,7 +141,7 @@ __global__ __launch_bounds__(kSelBlock) void k_sel_hist(const Elem* __restrict__
     if (threadIdx.x == 0) {
       uint64_t o = 0, no = 0;
 #pragma unroll
-      for (int ww = 0; ww < kSelWaves; ++ww) {
+      for (int ww = 0; ww < kTileWaves; ++ww) {
         o |= span_or[ww];
         no |= span_nor[ww];
       }
@@ -161,18 +151,18 @@ __global__ __launch_bounds__(kSelBlock) void k_sel_hist(const Elem* __restrict__
   }
 }
 
-// One wave's kSelWaveRecs records from position wave0 on, lane-striped as in
+// One wave's kTileWaveRecs records from position wave0 on, lane-striped as in
 // lsb_runs.hip's wave_heads: item j of lane l is position wave0 + 64 j + l,
 // every load instruction reads 1 KiB of adjacent records in 16-byte accesses.
 // lt[j], eq[j] = ballots of the item's keys below and equal to the pivot
 // (positions >= here have neither).  Every lane of the wave must call it.
 template <bool VALS>
 __device__ __forceinline__ void wave_compare(const Elem* __restrict__ A, int64_t here, int64_t wave0, uint64_t pivot,
-                                             uint64_t (&key)[kSelItems], uint64_t (&val)[kSelItems],
-                                             uint64_t (&lt)[kSelItems], uint64_t (&eq)[kSelItems]) {
-  const int lane = sel_lane();
+                                             uint64_t (&key)[kTileItems], uint64_t (&val)[kTileItems],
+                                             uint64_t (&lt)[kTileItems], uint64_t (&eq)[kTileItems]) {
+  const int lane = tile_lane();
 #pragma unroll
-  for (int j = 0; j < kSelItems; ++j) {
+  for (int j = 0; j < kTileItems; ++j) {
     const int64_t i = wave0 + j * 64 + lane;
     ulonglong2 v = make_ulonglong2(0, 0);
     if (i < here) v = *reinterpret_cast<const ulonglong2*>(A + i);
@@ -182,29 +172,29 @@ __device__ __forceinline__ void wave_compare(const Elem* __restrict__ A, int64_t
     if constexpr (!VALS) asm volatile("" ::"v"(v.y));
   }
 #pragma unroll
-  for (int j = 0; j < kSelItems; ++j) {
+  for (int j = 0; j < kTileItems; ++j) {
     const bool in = wave0 + j * 64 + lane < here;
     lt[j] = __ballot(in && key[j] < pivot);
     eq[j] = __ballot(in && key[j] == pivot);
   }
 }
 
-__global__ __launch_bounds__(kSelBlock) void k_sel_count(const Elem* __restrict__ A, int64_t here, int64_t tiles,
+__global__ __launch_bounds__(kTileBlock) void k_sel_count(const Elem* __restrict__ A, int64_t here, int64_t tiles,
                                                          uint64_t pivot, uint32_t* __restrict__ tile_cnt) {
-  __shared__ uint32_t s_cnt[kSelWaves];
+  __shared__ uint32_t s_cnt[kTileWaves];
   const int wave = (int)(threadIdx.x >> 6);
   for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    uint64_t key[kSelItems], val[kSelItems], lt[kSelItems], eq[kSelItems];
-    wave_compare<false>(A, here, tile * kTile + (int64_t)wave * kSelWaveRecs, pivot, key, val, lt, eq);
+    uint64_t key[kTileItems], val[kTileItems], lt[kTileItems], eq[kTileItems];
+    wave_compare<false>(A, here, tile * kTile + (int64_t)wave * kTileWaveRecs, pivot, key, val, lt, eq);
     uint32_t cnt = 0;  // the same in every lane
 #pragma unroll
-    for (int j = 0; j < kSelItems; ++j) cnt += (uint32_t)__popcll(lt[j]) | ((uint32_t)__popcll(eq[j]) << 16);
-    if (sel_lane() == 0) s_cnt[wave] = cnt;
+    for (int j = 0; j < kTileItems; ++j) cnt += (uint32_t)__popcll(lt[j]) | ((uint32_t)__popcll(eq[j]) << 16);
+    if (tile_lane() == 0) s_cnt[wave] = cnt;
     __syncthreads();
     if (threadIdx.x == 0) {
       uint32_t total = 0;
 #pragma unroll
-      for (int w = 0; w < kSelWaves; ++w) total += s_cnt[w];
+      for (int w = 0; w < kTileWaves; ++w) total += s_cnt[w];
       tile_cnt[tile] = total;
     }
     __syncthreads();
@@ -261,8 +251,8 @@ __device__ __forceinline__ void store_range(T* __restrict__ col, int64_t g0, int
     groups = (cnt - head) / G;
   }
   const int tail0 = head + groups * G;
-  for (int i = threadIdx.x; i < head; i += kSelBlock) col[g0 + i] = (T)lds[i];
-  for (int g = threadIdx.x; g < groups; g += kSelBlock) {
+  for (int i = threadIdx.x; i < head; i += kTileBlock) col[g0 + i] = (T)lds[i];
+  for (int g = threadIdx.x; g < groups; g += kTileBlock) {
     const int i = head + g * G;
     if constexpr (sizeof(T) == 8)
       *reinterpret_cast<u64x2*>(col + g0 + i) = u64x2{lds[i], lds[i + 1]};
@@ -270,7 +260,7 @@ __device__ __forceinline__ void store_range(T* __restrict__ col, int64_t g0, int
       *reinterpret_cast<u32x4*>(col + g0 + i) =
           u32x4{(uint32_t)lds[i], (uint32_t)lds[i + 1], (uint32_t)lds[i + 2], (uint32_t)lds[i + 3]};
   }
-  for (int i = tail0 + threadIdx.x; i < cnt; i += kSelBlock) col[g0 + i] = (T)lds[i];
+  for (int i = tail0 + threadIdx.x; i < cnt; i += kTileBlock) col[g0 + i] = (T)lds[i];
 }
 
 // The selected records of a tile lie at adjacent indices of the outputs: the
@@ -283,38 +273,25 @@ __device__ __forceinline__ void store_range(T* __restrict__ col, int64_t g0, int
 // recount must equal the count's tile_cnt; otherwise A has changed since,
 // *err is set and the tile writes nothing.  No index leaves [0, take).
 template <typename KeyT, int ValBytes, bool VEC>
-__global__ __launch_bounds__(kSelBlock) void k_sel_write(const Elem* __restrict__ A, int64_t here, int64_t tiles,
+__global__ __launch_bounds__(kTileBlock) void k_sel_write(const Elem* __restrict__ A, int64_t here, int64_t tiles,
                                                          uint64_t pivot, int64_t share, int64_t take,
                                                          const uint32_t* __restrict__ tile_cnt,
                                                          const int64_t* __restrict__ tile_base,
                                                          KeyT* __restrict__ keys, int key_type, int flags,
                                                          void* __restrict__ vals, uint32_t* __restrict__ err) {
-  __shared__ uint32_t s_cell[kSelCells];
+  __shared__ uint32_t s_cell[kTileCells];
   __shared__ uint32_t s_total;
   __shared__ uint64_t s_key[kTile];
   __shared__ uint64_t s_val[ValBytes ? kTile : 1];
-  const int lane = sel_lane(), wave = (int)(threadIdx.x >> 6);
+  const int lane = tile_lane(), wave = (int)(threadIdx.x >> 6);
   const KeyForm form = key_form(key_type, flags);
   for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    uint64_t key[kSelItems], val[kSelItems], lt[kSelItems], eq[kSelItems];
-    const int64_t wave0 = tile * kTile + (int64_t)wave * kSelWaveRecs;
+    uint64_t key[kTileItems], val[kTileItems], lt[kTileItems], eq[kTileItems];
+    const int64_t wave0 = tile * kTile + (int64_t)wave * kTileWaveRecs;
     wave_compare<ValBytes != 0>(A, here, wave0, pivot, key, val, lt, eq);
-#pragma unroll
-    for (int j = 0; j < kSelItems; ++j)
-      if (lane == j) s_cell[wave * kSelItems + j] = (uint32_t)__popcll(lt[j]) | ((uint32_t)__popcll(eq[j]) << 16);
-    __syncthreads();
-    if (wave == 0) {  // cell counts -> exclusive prefixes, and their total (both halves at once: no carry, kTile < 2^16)
-      const uint32_t c = s_cell[lane];
-      uint32_t incl = c;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += o;
-      }
-      s_cell[lane] = incl - c;
-      if (lane == 63) s_total = incl;
-    }
-    __syncthreads();
+    // both counts in one word, scanned at once: no carry between the halves, kTile < 2^16
+    tile_cells(s_cell, &s_total,
+               [&](int j) { return (uint32_t)__popcll(lt[j]) | ((uint32_t)__popcll(eq[j]) << 16); });
     const int64_t lt0 = tile_base[2 * tile], eq0 = tile_base[2 * tile + 1];
     const int64_t taken0 = eq0 < share ? eq0 : share;  // equal keys taken in the tiles before
     const int64_t out0 = lt0 + taken0;
@@ -325,12 +302,12 @@ __global__ __launch_bounds__(kSelBlock) void k_sel_write(const Elem* __restrict_
       if (threadIdx.x == 0) atomicOr(err, 1u);
     } else {
 #pragma unroll
-      for (int j = 0; j < kSelItems; ++j) {
-        const uint32_t cell = s_cell[wave * kSelItems + j];
-        const int64_t e = eq0 + (int64_t)(cell >> 16) + sel_mbcnt(eq[j]);  // equal keys in front of this record
+      for (int j = 0; j < kTileItems; ++j) {
+        const uint32_t cell = s_cell[wave * kTileItems + j];
+        const int64_t e = eq0 + (int64_t)(cell >> 16) + tile_mbcnt(eq[j]);  // equal keys in front of this record
         const bool is_lt = (lt[j] >> lane) & 1, is_eq = (eq[j] >> lane) & 1;
         if (is_lt || (is_eq && e < share)) {
-          const int at = (int)(cell & 0xffffu) + (int)sel_mbcnt(lt[j]) + (int)((e < share ? e : share) - taken0);
+          const int at = (int)(cell & 0xffffu) + (int)tile_mbcnt(lt[j]) + (int)((e < share ? e : share) - taken0);
           if (keys) s_key[at] = decode(key[j], form);
           if constexpr (ValBytes != 0) s_val[at] = val[j];
         }
@@ -355,7 +332,7 @@ void select_write_form(const Elem* A, int64_t here, uint64_t pivot, int64_t shar
                        const uint32_t* tile_cnt, const int64_t* tile_base, void* keys, int key_type, int flags,
                        void* vals, uint32_t* err, hipStream_t s) {
   const int64_t tiles = run_tiles(here);
-  const dim3 grid(sel_grid(tiles)), block(kSelBlock);
+  const dim3 grid(sel_grid(tiles)), block(kTileBlock);
   if (aligned16(keys) && aligned16(vals))
     hipLaunchKernelGGL((k_sel_write<KeyT, ValBytes, true>), grid, block, 0, s, A, here, tiles, pivot, share, take,
                        tile_cnt, tile_base, static_cast<KeyT*>(keys), key_type, flags, vals, err);
@@ -372,7 +349,7 @@ hipError_t launch_select_hist(const Elem* src, int64_t m, int shift, uint64_t pr
       (dst && bound <= 0))
     return hipErrorInvalidValue;
   const int64_t tiles = run_tiles(m);
-  const dim3 grid(sel_grid(tiles)), block(kSelBlock);
+  const dim3 grid(sel_grid(tiles)), block(kTileBlock);
   unsigned long long* w = reinterpret_cast<unsigned long long*>(words);
   if (span)
     hipLaunchKernelGGL((k_sel_hist<true, false>), grid, block, 0, s, src, m, tiles, shift, prefix, mask, dst, bound, w);
@@ -388,7 +365,7 @@ hipError_t launch_select_count(const Elem* A, int64_t here, uint64_t pivot, int6
                                uint32_t* tile_cnt, int64_t* tile_base, uint32_t* err, hipStream_t s) {
   if (here <= 0 || !A || !tile_cnt || !tile_base || !err || below < 0 || equal < 0) return hipErrorInvalidValue;
   const int64_t tiles = run_tiles(here);
-  hipLaunchKernelGGL(k_sel_count, dim3(sel_grid(tiles)), dim3(kSelBlock), 0, s, A, here, tiles, pivot, tile_cnt);
+  hipLaunchKernelGGL(k_sel_count, dim3(sel_grid(tiles)), dim3(kTileBlock), 0, s, A, here, tiles, pivot, tile_cnt);
   hipLaunchKernelGGL(k_sel_scan, dim3(1), dim3(kSelScanBlock), 0, s, tiles, tile_cnt, tile_base, below, equal, err);
   return hipGetLastError();
 }

@@ -17,7 +17,7 @@ H=/opt/rocm/bin/hipcc
 F="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -I$S/include -I$S/distributed-lsb_amd/csrc $*"
 objs=()
 for src in "$S"/distributed-lsb_amd/csrc/*.hip "$S"/distributed-lsb_amd/csrc/*.cpp; do
-  o="$out/$(basename "${src%.*}").o"
+  o="$out/$(basename "$src" | tr . _).o"  # lsb_runs.hip and lsb_runs.cpp are two units
   $H $F -c "$src" -o "$o" &
   objs+=("$o")
 done
