@@ -443,6 +443,7 @@ int sort_body(lsb_ctx* c) {
   c->last_first = LSB_FIRST_COUNT;
   c->last_records = LSB_RECORDS_FULL;
   c->last_packed_tile = 0;
+  std::fill(c->pass_tile, c->pass_tile + LSB_MAX_PASSES, 0);
   c->pass_cursor = 0;
   c->cur_pass = 0;
   if (c->bits == 64 && exchanging(c)) {
@@ -514,6 +515,15 @@ int lsb_get_last_packed_tile(lsb_ctx_t* c, int* records) {
   LSB_TRY(check_ctx(c));
   if (!records) return fail(LSB_ERR_INVALID, "lsb_get_last_packed_tile", "null");
   *records = c->last_packed_tile;
+  return LSB_OK;
+}
+
+int lsb_get_last_pass_tiles(lsb_ctx_t* c, int* records, int max_passes, int* passes) {
+  LSB_TRY(check_ctx(c));
+  if (!records || !passes || max_passes < 0) return fail(LSB_ERR_INVALID, "lsb_get_last_pass_tiles", "null");
+  const int n = std::min(std::min(c->last_local_passes, (int)LSB_MAX_PASSES), max_passes);
+  for (int i = 0; i < n; ++i) records[i] = c->pass_tile[i];
+  *passes = n;
   return LSB_OK;
 }
 

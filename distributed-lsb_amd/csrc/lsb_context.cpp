@@ -417,6 +417,14 @@ lsb_ctx* new_ctx(int64_t n_total, int num_ranks, int radix_bits) {
     const int v = atoi(e);
     if (lsb::onesweep_packed_tile_ok(v)) c->packed_tile = v;
   }
+  // LSB_EDGE_TILES=mask: which edge passes of a packed sort may take the
+  // large tile where its middle passes take 5120 (lsb::os_edge_applies):
+  // 1 the first pass, 2 the pass that reads the regional layout, 4 the last pass (A/B runs and
+  // tests; with LSB_PACKED_TILE=4096 or 4608 every edge pass keeps 4096).
+  if (const char* e = getenv("LSB_EDGE_TILES")) {
+    const int v = atoi(e);
+    if (v >= 0 && (unsigned)v <= lsb::kOsEdgeAll && ((unsigned)v & ~lsb::kOsEdgeAll) == 0) c->edge_tiles = (unsigned)v;
+  }
   // LSB_EXCHANGE_CHUNKS=C: contexts start with LSB_OPT_EXCHANGE_CHUNKS = C
   // (A/B runs of programs that do not set options); LSB_XCHUNK_RESERVE: the
   // chunk passes' grid leaves that many workgroups to the wire (experiments).

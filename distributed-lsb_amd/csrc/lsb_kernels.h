@@ -115,10 +115,13 @@ inline int64_t onesweep_tiles(int64_t m) { return (m + kTile - 1) / kTile; }
 // The packed middle passes (Packed -> Packed counting the next digit, no
 // regional layout) may take larger tiles: their stage costs 12 bytes per
 // record, so 512 threads x 10 records still fit two workgroups per CU
-// (kOsTile10; kOsTile9 is the size between, for measurements).  Every other
-// instance keeps kTile.  A pass counts the next digit per sub-array of the
-// next pass's input, so it is told the next pass's tile size (tn) as well as
-// its own (t).
+// (kOsTile10; kOsTile9 is the size between, for measurements).  A packed
+// sort's edge passes have kOsTile10 instances too (lsb_ostile.h
+// os_edge_applies: the packing first pass, the pass that reads the regional
+// layout where its regions are whole tiles of that size, and the last pass,
+// which stages keys and 32-bit values apart).  Every other instance keeps
+// kTile.  A pass counts the next digit per sub-array of the next pass's
+// input, so it is told the next pass's tile size (tn) as well as its own (t).
 constexpr int kOsTile9 = kOsBlock * 9;    // 4608
 constexpr int kOsTile10 = kOsBlock * 10;  // 5120
 inline bool onesweep_packed_tile_ok(int t) { return t == kTile || t == kOsTile9 || t == kOsTile10; }
@@ -305,8 +308,8 @@ struct OnesweepExtra {
   // Packed -> Elem.
   bool pack_in = false, pack_out = false;
   // Records per tile of this pass's input and of the next pass's (0: kTile).
-  // kOsTile9 / kOsTile10 only for a packed middle pass (tile) and for the
-  // packed pass before one (next_tile), and only where onesweep_tile_fits.
+  // Over kTile only in the combinations of os_pass_tiles_ok (lsb_ostile.h: a
+  // packed sort's passes), and only where onesweep_tile_fits.
   int tile = 0, next_tile = 0;
 };
 // The runtime's choice of OnesweepExtra::halves for a rank, from a digit's

@@ -1047,18 +1047,27 @@ __device__ __forceinline__ void onesweep_body(
   // Per-wave digit counters -> tile positions (< T <= 5120): 16-bit at 8 waves,
   // so the counters of two workgroups still fit a CU beside their stages.
   static_assert(T < 0xFFFF && T % BLOCK == 0, "16-bit tile positions; 0xFFFF is cut's `never`");
-  // A tile larger than kTile (the packed middle passes, kOsTile10): ten
-  // records in flight leave no room for the histogram column (re-read on a
-  // sub-array change, as the split stage does) nor for a register per rank
-  // (two 16-bit ranks share one).
+  // A tile larger than kTile (a packed sort's passes: the packing first pass,
+  // the pass that reads the regional layout, the middle passes, the last
+  // pass; kOsTile10): ten records in flight leave no room for the histogram
+  // column (re-read on a sub-array change, as the split stage does) nor for
+  // a register per rank (two 16-bit ranks share one).  The packing first pass
+  // folds each 16-byte record to a Packed one as it lands (the value's high
+  // word goes into vhi), so only the loads' destinations hold 40 registers.
   constexpr bool kBig = T > kTile;
-  static_assert(!kBig || (PIN && POUT && NEXT && RG == 0), "large tiles: the packed middle passes only");
+  static_assert(!kBig || (PIN && RG != 1 && POUT == NEXT) || (RG == 1 && POUT), "large tiles: a packed sort's passes");
+  using RReg = typename std::conditional<kBig, Packed, RIn>::type;  // a record in registers
+  // The stage as keys and 32-bit values apart: a packed output, and the large
+  // tile's whole-record output (its values are widened at the write-out; as
+  // whole records 5120 of them would take 80 KiB).
+  constexpr bool kKV = POUT || kBig;
+  using RStage = typename std::conditional<kKV, Packed, Elem>::type;
   using WC = typename std::conditional<(W > 4), uint16_t, uint32_t>::type;
 
   constexpr int HT = T / HALVES;                // staged records per half
-  __shared__ Elem stage[POUT ? 1 : HT];         // the ranked tile (64 KiB, or one half)
-  __shared__ uint64_t skey[POUT ? HT : 1];      // POUT: its keys and values (48 KiB)
-  __shared__ uint32_t sval[POUT ? HT : 1];
+  __shared__ Elem stage[kKV ? 1 : HT];          // the ranked tile (64 KiB, or one half)
+  __shared__ uint64_t skey[kKV ? HT : 1];       // kKV: its keys and values (48 KiB; 60 for the large tile)
+  __shared__ uint32_t sval[kKV ? HT : 1];
   __shared__ WC wcnt[W][kBuckets];              // per-wave digit counters -> positions
   __shared__ int64_t delta[kBuckets];           // global dest = delta[digit] + tile position
   __shared__ uint32_t cut[NEXT ? kBuckets : 1];  // next-pass sub-array of a run: see below
@@ -1223,7 +1232,7 @@ __device__ __forceinline__ void onesweep_body(
       tb = region_base(rg_reg, rg.cap) + (int64_t)rg_k * T;
     }
 
-    RIn e[IPT];
+    RReg e[IPT];
     const int wbase = w * 64 * IPT + (int)lane;
     if (GATHER) {
       const int dn = __builtin_amdgcn_readfirstlane(s_desc.n);
@@ -1299,16 +1308,26 @@ __device__ __forceinline__ void onesweep_body(
       // zeros: the whole offset goes through the descriptor's range check
       // (a scalar offset operand would not).
       typedef uint32_t v3u __attribute__((ext_vector_type(3)));
-      const int64_t tbu = (int64_t)__builtin_amdgcn_readfirstlane(tile) * T;
-      const int nvu = (int)((m - tbu) < T ? (m - tbu) : T);
+      // (RG = 2: the tile's T slots, all inside the buffer; tb is uniform.)
+      const int64_t tbu = RG == 2 ? tb : (int64_t)__builtin_amdgcn_readfirstlane(tile) * T;
+      const int nvu = RG == 2 ? T : (int)((m - tbu) < T ? (m - tbu) : T);
       const __amdgpu_buffer_rsrc_t ri = __builtin_amdgcn_make_buffer_rsrc(
           const_cast<RIn*>(in + tbu), 0, nvu * (int)sizeof(RIn), 0x00020000);
       uint32_t vb = (uint32_t)wbase * (uint32_t)sizeof(RIn);
       asm volatile("" : "+v"(vb));
 #pragma unroll
       for (int i = 0; i < IPT; ++i) {
-        const v3u x = __builtin_amdgcn_raw_buffer_load_b96(ri, vb + (uint32_t)(i * 64 * (int)sizeof(RIn)), 0, 2);
-        e[i] = RIn{x.x, x.y, x.z};
+        if constexpr (PIN) {
+          const v3u x = __builtin_amdgcn_raw_buffer_load_b96(ri, vb + (uint32_t)(i * 64 * (int)sizeof(RIn)), 0, 2);
+          e[i] = Packed{x.x, x.y, x.z};
+        } else {
+          // A whole record: key, the value's low word, and its high word
+          // folded into vhi (the packing first pass).
+          typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+          const v4u x = __builtin_amdgcn_raw_buffer_load_b128(ri, vb + (uint32_t)(i * 64 * (int)sizeof(RIn)), 0, 2);
+          e[i] = Packed{x.x, x.y, x.z};
+          vhi |= x.w;
+        }
       }
     } else {
 #pragma unroll
@@ -1326,11 +1345,11 @@ __device__ __forceinline__ void onesweep_body(
         }
         if (!PIN && POUT) vhi |= (uint32_t)(rec_val(e[i]) >> 32);
       }
-      if (RG == 2) {
-        __builtin_amdgcn_sched_barrier(0);
-        const int64_t v = (int64_t)rg.counts[rg_reg] - (int64_t)rg_k * T;
-        nvalid = (int)(v < 0 ? 0 : (v < T ? v : T));
-      }
+    }
+    if (RG == 2 && !GATHER) {
+      __builtin_amdgcn_sched_barrier(0);
+      const int64_t v = (int64_t)rg.counts[rg_reg] - (int64_t)rg_k * T;
+      nvalid = (int)(v < 0 ? 0 : (v < T ? v : T));
     }
 #ifdef LSB_OS_PROFILE
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1428,7 +1447,7 @@ __device__ __forceinline__ void onesweep_body(
       for (int i = 0; i < IPT; ++i) {
         if (wbase + i * 64 < nvalid) {
           const uint32_t d = (uint32_t)(rec_key(e[i]) >> shift) & (kBuckets - 1);
-          if (POUT) {
+          if (kKV) {
             const uint32_t p = wcnt[w][d] + rank_of(i);
             skey[p] = rec_key(e[i]);
             sval[p] = (uint32_t)rec_val(e[i]);
@@ -1518,14 +1537,15 @@ __device__ __forceinline__ void onesweep_body(
     // emit: one staged record (tile position j, output slot delta + pos) to
     // memory, and its next digit to the sub-array histogram.
     // g = delta[digit] + the record's slot in its run, c = cut[digit].
-    auto emit = [&](auto skew_tag, const ROut& v, int j, int64_t g, uint32_t c) {
+    auto emit = [&](auto skew_tag, const RStage& v, int j, int64_t g, uint32_t c) {
       constexpr bool kSkew = decltype(skew_tag)::value;
       LSB_DASSERT(g >= 0 && g < mcap);
       // In range by construction.  The clamp keeps a look-back that gave up
       // (err set, output reported invalid) from storing outside `out`; a
       // clamp, not a branch: the conditional store cost 6 % of the sort.
       const uint64_t gs = (uint64_t)g < (uint64_t)(mcap - 1) ? (uint64_t)g : (uint64_t)(mcap - 1);
-      store_elem(out + gs, v);
+      if constexpr (std::is_same<RStage, ROut>::value) store_elem(out + gs, v);
+      else store_elem(out + gs, make_rec<ROut>(rec_key(v), rec_val(v)));  // the value widened
       if (NEXT) {
         const uint32_t xs = (uint32_t)j >= (c & 0xFFFFu) ? (c >> 24) : ((c >> 16) & 0xFFu);
         const uint32_t dn = (uint32_t)(rec_key(v) >> next_shift) & (kBuckets - 1);
@@ -1660,10 +1680,10 @@ __device__ __forceinline__ void onesweep_body(
         if constexpr (kBig) asm volatile("" : "+v"(tq));
 #pragma unroll
         for (int k0 = 0; k0 < HT / BLOCK; k0 += G) {
-          ROut v[G];
+          RStage v[G];
           int64_t dl[G];
           uint32_t ct[G];
-          if constexpr (POUT) {
+          if constexpr (kKV) {
             uint64_t kk[G];
 #pragma unroll
             for (int k = 0; k < G; ++k) kk[k] = skey[(k0 + k) * BLOCK + t];
@@ -1689,8 +1709,8 @@ __device__ __forceinline__ void onesweep_body(
         return;
       }
       for (int j = h * HT + t; j < jend; j += BLOCK) {
-        ROut v;
-        if constexpr (POUT) v = make_rec<Packed>(skey[j], sval[j]);
+        RStage v;
+        if constexpr (kKV) v = make_rec<Packed>(skey[j], sval[j]);
         else v = stage[j - h * HT];
         int pos = j;
         if constexpr (SEG) pos = seg_pos(v, j, jend);
@@ -2482,22 +2502,24 @@ hipError_t launch_onesweep(const Elem* in, Elem* out, int64_t m, int shift, int 
   if (e != hipSuccess) return e;
   const int rm = extra.region_mode;
   const RegionPass rp = extra.region ? *extra.region : RegionPass();
-  if (rm < 0 || rm > 2 || (rm != 0 && (!extra.region || rp.cap <= 0 || rp.cap % kTile != 0 ||
+  // Records per tile of this pass and of the next (over kTile: the passes of
+  // a packed sort that read packed records, lsb_kernels.h): the instances
+  // built are os_pass_tiles_ok's table (lsb_ostile.h).
+  const int T = extra.tile ? extra.tile : kTile, TN = extra.next_tile ? extra.next_tile : kTile;
+  if (rm < 0 || rm > 2 || (rm != 0 && (!extra.region || rp.cap <= 0 || rp.cap % kTile != 0 || (rm == 2 && rp.cap % T != 0) ||
                                        rp.cap * kRegions < m || !rp.counts)))
     return hipErrorInvalidValue;
-  // Records per tile of this pass and of the next (over kTile: the packed
-  // middle passes only, lsb_kernels.h).  A middle pass is followed by one of
-  // its own tile size or by the last pass (kTile); the pass that reads the
-  // regional layout (kTile) by a middle pass of any size.
-  const int T = extra.tile ? extra.tile : kTile, TN = extra.next_tile ? extra.next_tile : kTile;
-  const bool mid = rm == 0 && extra.pack_in && extra.pack_out && next_shift >= 0;  // a packed middle pass
-  const bool before_mid = extra.pack_out && next_shift >= 0 && (mid || (rm == 2 && extra.pack_in));
-  if (!onesweep_packed_tile_ok(T) || !onesweep_packed_tile_ok(TN) || (T != kTile && !mid) ||
-      (TN != kTile && !before_mid) || (mid && TN != kTile && TN != T) ||
-      (next_shift >= 0 && !onesweep_tile_fits(T, TN, m)))
+  const OsPassKind kind = rm == 1                                ? kOsPassFirst
+                          : rm == 2                              ? kOsPassLayout
+                          : extra.pack_in && next_shift >= 0     ? kOsPassMiddle
+                          : extra.pack_in                        ? kOsPassLast
+                                                                 : kOsPassOther;
+  if (!os_pass_tiles_ok(kind, T, next_shift >= 0 ? TN : kTile, kTile) ||
+      ((T != kTile || TN != kTile) && !extra.pack_in && !(rm == 1 && extra.pack_out)) ||
+      (next_shift >= 0 && rm != 1 && !onesweep_tile_fits(T, TN, m)))
     return hipErrorInvalidValue;
   // Tiles of the input: the regional layout's slots for its reading pass.
-  const int64_t TT = rm == 2 ? rp.cap / kTile * kRegions : (m + T - 1) / T;
+  const int64_t TT = rm == 2 ? os_rows_track2(rp.cap, T, kRegions) : (m + T - 1) / T;
   auto* c16 = reinterpret_cast<unsigned long long*>(extra.count16);
   const bool gat = extra.gather != nullptr;
   // The split stage only for the plain and next-digit forms, never gathered
@@ -2538,7 +2560,11 @@ hipError_t launch_onesweep(const Elem* in, Elem* out, int64_t m, int shift, int 
       if (e == hipSuccess) e = hipMemsetAsync(rp.ovf, 0, sizeof(uint32_t), s);
       if (e == hipSuccess && extra.pack_out) e = hipMemsetAsync(rp.wide, 0, sizeof(uint32_t), s);
       if (e != hipSuccess) return e;
-      if (extra.pack_out)
+      if (extra.pack_out && T == kOsTile10)  // the packing first pass in large tiles
+        hipLaunchKernelGGL((k_onesweep<kOsBlock, 10, true, false, 1, false, false, 1, false, true>), gd, bd, 0, s,
+                           in, out, m, shift, next_shift, sub_hist, next_hist, st, tile_ctr, epoch, err, nullptr,
+                           nullptr, SegPass(), gsrc, rp);
+      else if (extra.pack_out)
         hipLaunchKernelGGL((k_onesweep<kOsBlock, kOsIpt, true, false, 1, false, false, 1, false, true>), gd, bd, 0, s,
                            in, out, m, shift, next_shift, sub_hist, next_hist, st, tile_ctr, epoch, err, nullptr,
                            nullptr, SegPass(), gsrc, rp);
@@ -2547,7 +2573,11 @@ hipError_t launch_onesweep(const Elem* in, Elem* out, int64_t m, int shift, int 
                            m, shift, next_shift, sub_hist, next_hist, st, tile_ctr, epoch, err, nullptr, nullptr,
                            SegPass(), gsrc, rp);
     } else if (next_shift >= 0 && extra.pack_in) {
-      if (TN == kOsTile10)
+      if (T == kOsTile10)  // the layout in large tiles (cap a multiple of them); TN = T
+        hipLaunchKernelGGL((k_onesweep<kOsBlock, 10, true, false, 1, false, false, 2, true, true, kOsTile10>),
+                           gd, bd, 0, s, in, out, m, shift, next_shift, sub_hist, next_hist, st, tile_ctr, epoch, err,
+                           nullptr, nullptr, SegPass(), gsrc, rp);
+      else if (TN == kOsTile10)
         hipLaunchKernelGGL((k_onesweep<kOsBlock, kOsIpt, true, false, 1, false, false, 2, true, true, kOsTile10>),
                            gd, bd, 0, s, in, out, m, shift, next_shift, sub_hist, next_hist, st, tile_ctr, epoch, err,
                            nullptr, nullptr, SegPass(), gsrc, rp);
@@ -2595,6 +2625,10 @@ hipError_t launch_onesweep(const Elem* in, Elem* out, int64_t m, int shift, int 
         hipLaunchKernelGGL((k_onesweep<kOsBlock, kOsIpt, true, false, 1, false, false, 0, true, true>), gd, bd, 0, s,
                            in, out, m, shift, next_shift, sub_hist, next_hist, st, tile_ctr, epoch, err, nullptr,
                            nullptr, SegPass(), gsrc, RegionPass());
+    } else if (T == kOsTile10) {  // the last pass in large tiles: values widened at the write-out
+      hipLaunchKernelGGL((k_onesweep<kOsBlock, 10, false, false, 1, false, false, 0, true, false>), gd, bd, 0, s,
+                         in, out, m, shift, 0, sub_hist, nullptr, st, tile_ctr, epoch, err, nullptr, nullptr,
+                         SegPass(), gsrc, RegionPass());
     } else {
       hipLaunchKernelGGL((k_onesweep<kOsBlock, kOsIpt, false, false, 1, false, false, 0, true, false>), gd, bd, 0, s,
                          in, out, m, shift, 0, sub_hist, nullptr, st, tile_ctr, epoch, err, nullptr, nullptr,

@@ -63,6 +63,46 @@ LSB_HD inline bool os_big_applies(int64_t m, int big, int small) {
   return big > small && os_tile_fits(big, small, m) && os_tile_fits(big, big, m) && os_tile_fits(small, big, m);
 }
 
+// A packed sort's edge passes (the packing first pass, the pass that reads
+// the regional layout and the last pass) take the large tile too, each when
+// its bit of the context's setting is on.
+constexpr unsigned kOsEdgeFirst = 1u, kOsEdgeLayout = 2u, kOsEdgeLast = 4u;
+constexpr unsigned kOsEdgeAll = kOsEdgeFirst | kOsEdgeLayout | kOsEdgeLast;
+constexpr int kOsEdgeTile = 5120;  // the only large tile the edge instances are built at
+// Which edge passes of a packed sort of m records over regions of `cap` slots
+// take `big` records per tile, where its middle passes do (big = 0: they do
+// not, nor does any edge pass).  The layout's tile k of a region is that
+// region's slots [k * big, (k + 1) * big), so whole tiles must fill `cap`.
+// The first pass writes regions, which no run crosses, whatever its tile;
+// every other seam is one os_big_applies already admits (small -> big,
+// big -> big, big -> small).
+LSB_HD inline unsigned os_edge_applies(int64_t m, int64_t cap, unsigned setting, int big, int small) {
+  if (big != kOsEdgeTile || !os_big_applies(m, big, small)) return 0u;
+  unsigned e = setting & kOsEdgeAll;
+  if (cap <= 0 || cap % big != 0) e &= ~kOsEdgeLayout;
+  return e;
+}
+// The kinds of pass launch_onesweep tells apart by tile size, and the
+// (kind, t, tn) combinations it has instances for: t records per tile, the
+// next pass's tn (ignored by a pass that counts no next digit).
+enum OsPassKind { kOsPassOther = 0, kOsPassFirst, kOsPassLayout, kOsPassMiddle, kOsPassLast };
+LSB_HD inline bool os_pass_tiles_ok(OsPassKind kind, int t, int tn, int small) {
+  const bool any_t = t == small || t == 4608 || t == kOsEdgeTile;
+  const bool any_tn = tn == small || tn == 4608 || tn == kOsEdgeTile;
+  switch (kind) {
+    case kOsPassFirst: return (t == small || t == kOsEdgeTile) && any_tn;  // regions: tn does not enter its counts
+    case kOsPassLayout: return (t == small && any_tn) || (t == kOsEdgeTile && tn == kOsEdgeTile);
+    case kOsPassMiddle: return any_t && (tn == t || tn == small);
+    case kOsPassLast: return t == small || t == kOsEdgeTile;
+    default: return t == small && tn == small;
+  }
+}
+// Look-back rows a launch writes: the first track's, over the m records, and
+// the second track's (the pass that reads the regional layout), over the
+// layout's slots.
+LSB_HD inline int64_t os_rows_track1(int64_t m, int t) { return os_tiles(m, t); }
+LSB_HD inline int64_t os_rows_track2(int64_t cap, int t, int regions) { return cap / t * regions; }
+
 // Look-back rows shared by launches of different tile counts.  Invariant:
 // after a launch of `rows` tiles at epoch e, the rows below `rows` carry e's
 // parity and the rows from there on are untrusted (an earlier, longer launch

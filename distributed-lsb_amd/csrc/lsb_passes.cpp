@@ -106,6 +106,7 @@ int onesweep_ensure(Rank& r) {
     LSB_TRY(dev_alloc(&r.os_status2, rows));
     HIP_TRY(hipMemsetAsync(r.os_status2, 0, rows * sizeof(uint32_t), r.stream));
     r.os_epoch2 = 0;
+    r.os_rows2 = lsb::os_rows_track2(r.rg_cap, lsb::kTile, lsb::kRegions);
   }
   return LSB_OK;
 }
@@ -120,9 +121,11 @@ int onesweep_ensure(Rank& r) {
 // launch zeroes them first and restarts the epochs (the first is odd).
 // The pass that reads the regional layout (region_mode 2) has more tiles
 // than the others and keeps its rows on a track of its own (os_status2,
-// os_epoch2).  A packed sort's middle passes have fewer (larger tiles) and
-// share os_status: a launch of more tiles than the one before first fills
-// the rows that launch left alone (lsb::status_fill; os_rows).
+// os_epoch2).  A packed sort's passes of larger tiles have fewer rows, on
+// either track (the layout in large tiles in a packed sort, in kTile tiles in
+// a sort of whole records): a launch of more tiles than the one before on its
+// track first fills the rows that launch left alone (lsb::status_fill;
+// os_rows, os_rows2).
 void zero_status(Rank& r) {
   (void)hipMemsetAsync(r.os_status, 0, (size_t)lsb::onesweep_tiles(r.here) * lsb::kBuckets * sizeof(uint32_t),
                        r.stream);
@@ -133,6 +136,7 @@ void zero_status(Rank& r) {
   r.os_epoch = 0;
   r.os_epoch2 = 0;
   r.os_rows = lsb::onesweep_tiles(r.here);  // every row of epoch 0's parity
+  r.os_rows2 = lsb::os_rows_track2(r.rg_cap, lsb::kTile, lsb::kRegions);
 }
 
 int onesweep_launch(lsb_ctx* c, Rank& r, int shift, int next, const uint32_t* hist,
@@ -145,6 +149,7 @@ int onesweep_launch(lsb_ctx* c, Rank& r, int shift, int next, const uint32_t* hi
   const bool track2 = x.region_mode == 2;
   uint32_t* status = track2 ? r.os_status2 : r.os_status;
   uint32_t& last_epoch = track2 ? r.os_epoch2 : r.os_epoch;
+  int64_t& last_rows = track2 ? r.os_rows2 : r.os_rows;
   if (!status) return fail(LSB_ERR_INVALID, "onesweep_launch", "regional layout's look-back rows");
   uint32_t epoch = last_epoch + 1;
   if (epoch >= (1u << 30)) epoch = 2;  // 2^30 is even: keep the alternation
@@ -153,16 +158,16 @@ int onesweep_launch(lsb_ctx* c, Rank& r, int shift, int next, const uint32_t* hi
     r.os_dirty = true;
     return fail(LSB_ERR_HIP, "launch_onesweep", "injected launch failure (LSB_OPT_FAIL_ONESWEEP)");
   }
-  const int64_t rows = lsb::onesweep_tiles_of(r.here, x.tile ? x.tile : lsb::kTile);
+  const int tile = x.tile ? x.tile : lsb::kTile;
+  const int64_t rows = track2 ? lsb::os_rows_track2(x.region ? x.region->cap : 0, tile, lsb::kRegions)
+                              : lsb::os_rows_track1(r.here, tile);
   {
     Timer t(c, &r, LSB_K_SCATTER);
     e = hipSuccess;
-    if (!track2) {
-      const lsb::StatusFill f = lsb::status_fill(r.os_rows, rows, epoch);
-      if (f.count > 0)
-        e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(status + f.first * lsb::kBuckets), (int)f.word,
-                              (size_t)f.count * lsb::kBuckets, r.stream);
-    }
+    const lsb::StatusFill f = lsb::status_fill(last_rows, rows, epoch);
+    if (f.count > 0)
+      e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(status + f.first * lsb::kBuckets), (int)f.word,
+                            (size_t)f.count * lsb::kBuckets, r.stream);
     if (e == hipSuccess)
       e = lsb::launch_onesweep(r.A, r.B, r.here, shift, next, hist, next_hist, status, r.os_ctr,
                                epoch, r.os_ctr + lsb::kOnesweepSubs, r.os_grid, r.stream, x);
@@ -173,7 +178,8 @@ int onesweep_launch(lsb_ctx* c, Rank& r, int shift, int next, const uint32_t* hi
     return fail(LSB_ERR_HIP, "launch_onesweep", hipGetErrorString(e));
   }
   last_epoch = epoch;
-  if (!track2) r.os_rows = rows;
+  last_rows = rows;
+  if (c->cur_pass >= 0 && c->cur_pass < LSB_MAX_PASSES) c->pass_tile[c->cur_pass] = tile;
   count_pass_elems(c, r.here);
   std::swap(r.A, r.B);
   return LSB_OK;
@@ -236,8 +242,18 @@ int onesweep_digits(lsb_ctx* c, Rank& r, const std::vector<int>& digits, int* pa
   // reads the regional layout and before the last) take the context's large
   // tile where it fits (lsb::onesweep_big_applies); the pass before one
   // counts the next digit by that size.
+  // The edge passes (the one that reads the regional layout, the last one)
+  // take it as well where lsb::os_edge_applies and the context's setting say.
   const int big = packed && lsb::onesweep_big_applies(r.here, c->packed_tile) ? c->packed_tile : 0;
+  const unsigned edge = lsb::os_edge_applies(r.here, rp ? rp->cap : 0, c->edge_tiles, big, lsb::kTile);
   auto middle = [&](size_t i) { return packed && i > from && i + 1 < digits.size(); };
+  auto tile_of = [&](size_t i) -> int {
+    if (i >= digits.size()) return 0;
+    if (middle(i)) return big;
+    if (packed && rp && i == from) return edge & lsb::kOsEdgeLayout ? big : 0;
+    if (packed && i > from) return edge & lsb::kOsEdgeLast ? big : 0;  // the last pass
+    return 0;
+  };
   for (size_t i = from; i < digits.size(); ++i) {
     const int shift = digits[i] * lsb::kDigitBits;
     const int next = i + 1 < digits.size() ? digits[i + 1] * lsb::kDigitBits : -1;
@@ -250,8 +266,8 @@ int onesweep_digits(lsb_ctx* c, Rank& r, const std::vector<int>& digits, int* pa
     }
     x.pack_in = packed;
     x.pack_out = packed && next >= 0;
-    x.tile = middle(i) ? big : 0;
-    x.next_tile = middle(i + 1) ? big : 0;
+    x.tile = tile_of(i);
+    x.next_tile = tile_of(i + 1);
     const int rc = onesweep_launch(c, r, shift, next, hist[i & 1], hist[(i + 1) & 1], x);
     if (rc != LSB_OK) {
       if (packed && i > from) {
@@ -355,6 +371,10 @@ int region_first(lsb_ctx* c, Rank& r, int shift, int next_shift, int* passes, bo
   x.region = &rp;
   x.region_mode = 1;
   x.pack_out = pack;
+  // A packed sort's first pass takes the large tile with its middle passes
+  // (lsb::os_edge_applies, as onesweep_digits decides for the other two).
+  const int big = pack && lsb::onesweep_big_applies(r.here, c->packed_tile) ? c->packed_tile : 0;
+  if (lsb::os_edge_applies(r.here, rp.cap, c->edge_tiles, big, lsb::kTile) & lsb::kOsEdgeFirst) x.tile = big;
   LSB_TRY(onesweep_launch(c, r, shift, next_shift, nullptr, r.os_hist + lsb::kOnesweepSubs * lsb::kBuckets, x));
   ++*passes;
   r.rg_h[kRgWide] = 0;

@@ -107,14 +107,15 @@ struct Rank {
   int os_grid = 0;                      // persistent grid (2 workgroups per CU)
   // The regional first pass (LSB_OPT_REGION_FIRST), allocated on first use:
   // the look-back rows of the pass that reads the regional layout (a track
-  // of their own: that pass has more tiles than the others, and a status
-  // buffer must only ever see one tile count), its epoch,
+  // of their own: that pass has more tiles than the others; launches of
+  // different tile counts on one track refill rows), its epoch,
   // and rg_buf: region counts, the sample's histogram and span, the overflow
   // word (kRg* offsets, lsb_passes.cpp), rg_h its pinned mirror.
   int64_t cap = 0;                      // records A and B hold (>= here)
   int64_t rg_cap = 0;                   // slots per region (0: no regional first pass)
   uint32_t* os_status2 = nullptr;
   uint32_t os_epoch2 = 0;
+  int64_t os_rows2 = 0;                 // os_status2 rows the last launch wrote (as os_rows)
   uint32_t* rg_buf = nullptr;
   uint32_t* rg_h = nullptr;
   // Per-digit exchange with single-read local passes (sort_exchange_onesweep):
@@ -208,6 +209,7 @@ struct lsb_ctx {
   int fail_onesweep = 0;      // LSB_OPT_FAIL_ONESWEEP: the n-th k_onesweep launch fails (tests)
   int pack_values = 1;        // LSB_OPT_PACK_VALUES: 0 never, 1 when the values fit 32 bits, 2 always try
   int packed_tile = lsb::kOsTile10;  // LSB_PACKED_TILE: records per tile of a packed sort's middle passes
+  unsigned edge_tiles = lsb::kOsEdgeAll;  // LSB_EDGE_TILES: the edge passes that may take the large tile too
   bool pack_wide = false;     // a packing first pass of this context met a value over 32 bits
   bool broken = false;        // a failed packed sort could not restore whole records: no more sorts
   int hybrid = 0;             // LSB_OPT_HYBRID: 0 off, 1 k byte passes (the last one
@@ -220,6 +222,7 @@ struct lsb_ctx {
   int last_first = 0;  // the first pass's form (lsb_get_first_pass)
   int last_records = 0;  // the records between the passes (lsb_get_last_records)
   int last_packed_tile = 0;  // records per tile of the packed middle passes (lsb_get_last_packed_tile)
+  int pass_tile[LSB_MAX_PASSES] = {};  // records per tile of each local pass (lsb_get_last_pass_tiles; 0: no k_onesweep)
   // The plan of the last lsb_count_runs (lsb_plan_runs over every rank's
   // summary), valid until an entry point that can change A (runs_invalidate).
   bool runs_valid = false;

@@ -198,6 +198,7 @@ def _lib() -> ctypes.CDLL:
             "lsb_get_first_pass": (i32, [vp, vp]),
             "lsb_get_last_records": (i32, [vp, vp]),
             "lsb_get_last_packed_tile": (i32, [vp, vp]),
+            "lsb_get_last_pass_tiles": (i32, [vp, vp, i32, vp]),
             "lsb_local_ranks": (i32, [vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
             "lsb_generate": (i32, [vp]),
             "lsb_generate_ex": (i32, [vp, i32, ctypes.c_double]),
@@ -252,7 +253,7 @@ def _lib() -> ctypes.CDLL:
         for name, (res, args) in sig.items():
             # An older build given through LSB_LIBRARY (A/B timing against the
             # parent commit) lacks the newest entry points; calling them there raises.
-            if name in ("lsb_get_last_packed_tile", "lsb_search") and not hasattr(L, name):
+            if name in ("lsb_get_last_packed_tile", "lsb_get_last_pass_tiles", "lsb_search") and not hasattr(L, name):
                 continue
             fn = getattr(L, name)
             fn.restype = res
@@ -1344,6 +1345,15 @@ class World:
         f = ctypes.c_int()
         _check(_lib().lsb_get_last_packed_tile(self._h, ctypes.byref(f)), "lsb_get_last_packed_tile")
         return int(f.value)
+
+    def last_pass_tiles(self) -> list:
+        """Records per tile of each local pass of the last my_sort, in pass
+        order (lsb_get_last_pass_tiles; LSB_PACKED_TILE, LSB_EDGE_TILES):
+        0 for a pass that was no k_onesweep launch."""
+        t = (ctypes.c_int * 16)()
+        n = ctypes.c_int()
+        _check(_lib().lsb_get_last_pass_tiles(self._h, t, 16, ctypes.byref(n)), "lsb_get_last_pass_tiles")
+        return [int(t[i]) for i in range(n.value)]
 
     def kernel_stats(self) -> dict:
         out = {}

@@ -826,6 +826,15 @@ int  lsb_get_last_records(lsb_ctx_t* ctx, int* form);
  * environment's LSB_PACKED_TILE = 4096 | 4608 | 5120, read when the context
  * is created, sets the size asked for.  0 when no such pass ran. */
 int  lsb_get_last_packed_tile(lsb_ctx_t* ctx, int* records);
+/* Records per tile of each local pass of the last lsb_sort, in pass order:
+ * records[i] for i < *passes <= max_passes (0: that pass was no k_onesweep
+ * launch).  In a packed sort whose middle passes take 5120, the first and
+ * the last pass take 5120 too, and so does the pass that reads the regional
+ * layout where the regions' slots are whole tiles of it (2^25, 2^29 and 2^30
+ * records; not 2^26 to 2^28 nor below 2^25); the environment's
+ * LSB_EDGE_TILES (1: the first pass, 2: the layout's pass, 4: the last;
+ * default 7), read when the context is created, names the ones that may. */
+int  lsb_get_last_pass_tiles(lsb_ctx_t* ctx, int* records, int max_passes, int* passes);
 /* == globalShuffle(A, B, digit): one pass, result in A. */
 int  lsb_pass(lsb_ctx_t* ctx, int digit);
 int  lsb_sync(lsb_ctx_t* ctx);

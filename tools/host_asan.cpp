@@ -662,6 +662,29 @@ static void onesweep_tile_cases(std::mt19937_64& rng) {
     CHECK(lsb::status_fill(t5, t4, 8).word == 0x80000000u, "even epoch: odd fill, not zero");
     CHECK(lsb::status_fill(t4, t5, 8).count == 0 && lsb::status_fill(t4, t4, 8).count == 0, "no fill for fewer rows");
   }
+  // The second track (the pass that reads the regional layout) at 2^30
+  // records, regions of 532480 slots: packed sorts read it in tiles of 5120,
+  // sorts of whole records and the hybrid in tiles of 4096, in any order.
+  {
+    const int64_t r4 = lsb::os_rows_track2(532480, 4096, 2048), r5 = lsb::os_rows_track2(532480, 5120, 2048);
+    CHECK(r4 == 130 * 2048 && r5 == 104 * 2048, "the layout's tiles at 2^30 records");
+    const std::vector<int64_t> seq = {r5, r4, r5, r4, r4, r5, r5, r4, r5};
+    CHECK(replay_rows(seq, std::vector<bool>(seq.size(), false), r4, 0, true) == 0, "packed and whole-record sorts on track 2");
+    CHECK(replay_rows(seq, std::vector<bool>(seq.size(), false), r4, 0, false) > 0, "track 2 without the fill");
+  }
+  // Which edge passes take the large tile (tools/edgetile_host.cpp has the
+  // search): the caps of 2^24, 2^25 and 2^30 records, the setting's bits,
+  // and nothing without large middle passes.
+  CHECK(lsb::os_edge_applies(int64_t(1) << 30, 532480, lsb::kOsEdgeAll, 5120, 4096) == lsb::kOsEdgeAll, "2^30: every edge pass");
+  CHECK(lsb::os_edge_applies(int64_t(1) << 25, 20480, lsb::kOsEdgeAll, 5120, 4096) == lsb::kOsEdgeAll, "2^25: every edge pass");
+  CHECK(lsb::os_edge_applies(int64_t(1) << 24, 12288, lsb::kOsEdgeAll, 5120, 4096) == (lsb::kOsEdgeFirst | lsb::kOsEdgeLast),
+        "2^24: 12288 slots are no whole large tiles");
+  CHECK(lsb::os_edge_applies(int64_t(1) << 30, 532480, lsb::kOsEdgeLayout, 5120, 4096) == lsb::kOsEdgeLayout, "the setting's bits");
+  CHECK(lsb::os_edge_applies(int64_t(1) << 30, 532480, lsb::kOsEdgeAll, 4096, 4096) == 0 &&
+            lsb::os_edge_applies(int64_t(1) << 30, 532480, lsb::kOsEdgeAll, 4608, 4096) == 0 &&
+            lsb::os_edge_applies(int64_t(1) << 30, 532480, lsb::kOsEdgeAll, 0, 4096) == 0,
+        "4096 and 4608 middle passes: every edge pass at 4096");
+  CHECK(lsb::os_edge_applies(61440, 4096, lsb::kOsEdgeAll, 5120, 4096) == 0, "too small for the large tile");
   // The applicability bound against a search: os_tile_fits must rule out
   // every m at which a run of t records could cover a whole non-empty
   // sub-array of the next pass and go on past it.
