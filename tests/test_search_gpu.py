@@ -15,6 +15,7 @@ reports what its namesake did there.
 import functools
 import inspect
 import os
+import re
 import subprocess
 import sys
 import xml.etree.ElementTree as ET
@@ -318,14 +319,18 @@ N = 20_003
 @functools.lru_cache(maxsize=None)
 def typed_keys(name, n=N, seed=20):
     """n keys of at most 2^12 distinct values spread over every byte of the
-    type, negative ones included; f32 without NaN and -0.0; f64 with both
-    zeros, both infinities and NaNs of both signs."""
+    type, negative ones included; f32 without NaN and -0.0 (test_every_key_form
+    has them); f64 with both zeros, both infinities and NaNs of both signs."""
     kt, dt = KEYS[name]
     v = np.random.default_rng(seed + kt).integers(0, 4096, n).astype(np.int64)
     if name == "i64":
         a = (v - 2048) * np.int64(0x0002_0008_0200_0801)
+    elif name == "u64":
+        a = v.astype(np.uint64) * np.uint64(0x0010_0401_0040_1001)  # up to the top bit
     elif name == "u32":
         a = (v * 0x00100401 % (1 << 32)).astype(np.uint32)
+    elif name == "i32":
+        a = ((v - 2048) * 0x00080201).astype(np.int32)
     else:
         a = ((v - 2048) * 0.37).astype(dt) * np.where(v % 3 == 0, dt(1e20), dt(1.0)).astype(dt)
         if name == "f64":
@@ -355,7 +360,8 @@ def typed_queries(name):
 
 
 @pytest.mark.parametrize("ranks", [1, 3])
-@pytest.mark.parametrize("name,descending", [("i64", False), ("f32", True), ("u32", False), ("f64", False)])
+@pytest.mark.parametrize("name,descending", [("i64", False), ("f32", True), ("u32", False), ("f64", False),
+                                             ("u64", False), ("i32", True)])
 @torch_first
 def test_typed_front_ends(lsb_built, name, descending, ranks):
     import torch
@@ -445,6 +451,103 @@ def test_fence_lifetime(lsb_built):
         w.copy_in(0, records(unsorted))
         w.my_sort()
         check_one_rank(w, second, q, "after my_sort")
+
+
+@torch_first
+def test_fence_lifetime_every_entry_point(lsb_built):
+    """Each call that can change A ends the fence table on its own: a search
+    right before it builds the table from other keys, every fence of which
+    differs from the keys after it.  (copy_in: test_fence_lifetime.)"""
+    L = lsb_built
+    n = 3 * TILE + 5
+    rng = np.random.default_rng(70)
+    first = np.sort(rng.integers(0, 1 << 40, n).astype(np.uint64))
+    second = np.sort(rng.integers(1 << 50, 1 << 60, n).astype(np.uint64))
+    one = np.uint64(1)
+    ends = np.array([0, U64_MAX], dtype=np.uint64)
+
+    def pool(keys):
+        return np.concatenate([first[::7], second[::7], first[::11] + one, keys[::5], keys[::13] + one, ends])
+
+    def load_first(w, vals=None):
+        """first's keys (values: vals, or the indices) and a search of them."""
+        rec = records(first)
+        if vals is not None:
+            rec["val"] = vals
+        w.copy_in(0, rec)
+        check_one_rank(w, first, pool(first), "first records")
+
+    def answers(w, q):
+        qt = column(q)
+        return {side: search(w, 0, qt, side) for side in SIDES}
+
+    def changed(w, before, what, expect=None):
+        """A's keys now: sorted, every fence another than before; the answers are theirs."""
+        keys = w.copy_out(0)["key"]
+        assert np.all(keys[1:] >= keys[:-1]), what
+        assert expect is None or np.array_equal(keys, expect), what
+        assert np.all(keys[::TILE] != before[::TILE]), what
+        check_one_rank(w, keys, pool(keys), what)
+
+    with L.World(n, ranks=1) as w:
+        # lsb_sort alone: the table is built from the generated, unsorted records first
+        load_first(w)
+        w.generate()
+        unsorted = w.copy_out(0)["key"]
+        assert not w.check_sorted()
+        got = answers(w, pool(first))  # unspecified counts, in bounds
+        assert all(g.min() >= 0 and g.max() <= n for g in got.values())
+        w.my_sort()
+        changed(w, unsorted, "after generate and my_sort", np.sort(unsorted))
+        # lsb_load_columns
+        load_first(w)
+        w.load_columns(0, column(second), key_type=0)
+        changed(w, first, "after load_columns", second)
+        # lsb_pass: the groups of the top byte in falling order, each sorted, so the stable pass on it sorts
+        load_first(w)
+        top_byte = second >> np.uint64(56)
+        assert np.unique(top_byte).size >= 8
+        groups = np.concatenate([second[top_byte == b] for b in np.unique(top_byte)[::-1]])
+        w.copy_in(0, records(groups))
+        assert not w.check_sorted()
+        got = answers(w, pool(second))
+        assert all(g.min() >= 0 and g.max() <= n for g in got.values())
+        w.global_shuffle(7)
+        changed(w, groups, "after global_shuffle", second)
+        # lsb_label_runs, lsb_scan_runs, BY_VALUE: the old values become the keys
+        load_first(w, vals=second)
+        w.count_runs()
+        w.label_runs(L.LABEL_BY_VALUE)
+        changed(w, first, "after label_runs(BY_VALUE)", second)
+        load_first(w, vals=second)
+        w.count_runs()
+        w.plan_scan(L.SCAN_SUM, L.KEY_U64)
+        w.scan_runs(L.LABEL_BY_VALUE)
+        changed(w, first, "after scan_runs(BY_VALUE)", second)
+        # KEEP changes no key: the same answers
+        load_first(w)
+        q = pool(first)
+        before = answers(w, q)
+        w.count_runs()
+        w.label_runs(L.LABEL_KEEP)
+        assert np.array_equal(w.copy_out(0)["key"], first)
+        after = answers(w, q)
+        assert all(np.array_equal(after[side], before[side]) for side in SIDES), "after label_runs(KEEP)"
+        w.count_runs()
+        w.plan_scan(L.SCAN_SUM, L.KEY_U64)
+        w.scan_runs(L.LABEL_KEEP)
+        assert np.array_equal(w.copy_out(0)["key"], first)
+        after = answers(w, q)
+        assert all(np.array_equal(after[side], before[side]) for side in SIDES), "after scan_runs(KEEP)"
+    # lsb_generate alone: one record is sorted whatever it holds
+    with L.World(1, ranks=1) as w:
+        old = np.array([U64_MAX], dtype=np.uint64)
+        w.copy_in(0, records(old))
+        check_one_rank(w, old, np.concatenate([old, old - one, ends]), "one record")
+        w.generate()
+        new = w.copy_out(0)["key"]
+        assert new[0] != old[0]
+        check_one_rank(w, new, np.concatenate([new, new - one, new + one, old, ends]), "after generate")
 
 
 # ------------------------------------------------- 8. refusals
@@ -559,3 +662,259 @@ def test_unsorted_records_stay_in_bounds(lsb_built):
                     got = host(full)
                     assert np.all(got[:pad] == SENT) and np.all(got[pad + m:] == SENT), (name, side, add)
                     assert got[pad:pad + m].min() >= 0 and got[pad:pad + m].max() <= n, (name, side, add)
+
+
+# ------------------------------------------------- 10. more tiles than staged fences
+def search_top():
+    src = open(os.path.join(ROOT, "distributed-lsb_amd", "csrc", "lsb_search.hip")).read()
+    return int(re.search(r"kSearchTop = (\d+);", src).group(1))
+
+
+def fence_levels(tiles, top):
+    """(step, tops, fences of the last staged group, its staged one included)
+    as k_search derives them from the rank's tiles."""
+    step = -(-tiles // top)
+    tops = -(-tiles // step)
+    return step, tops, tiles - (tops - 1) * step
+
+
+def sparse_keys(n, seed):
+    """n sorted distinct keys = 1 mod 4, so key - 1 and key + 1 miss and
+    nothing wraps: a running sum of random gaps, no sort."""
+    assert n << 37 < 1 << 62
+    gaps = np.random.default_rng(seed).integers(1, 1 << 37, n, dtype=np.int64)
+    return np.cumsum(gaps).astype(np.uint64) * np.uint64(4) + np.uint64(1)
+
+
+def staged_runs(n, step, tops):
+    """[a, b) record ranges that one value each fills, placed against the
+    staged fences s = a multiple of step (tiles [t0, t1] whole unless said):
+    [s - 1, s + 1], equal fences across a staged one; from step 3 on
+    [s + 1, s + step - 1], equal fences strictly between two staged ones;
+    [s, s + 2 step], equal adjacent staged ones; [s, s + step - 1], one staged
+    group exactly; a run that starts and ends inside tiles, over a group and
+    more; the last staged group up to the rank's last record."""
+    s = [step * (j * tops // 7) for j in range(1, 6)]
+
+    def whole(t0, t1):
+        return t0 * TILE, (t1 + 1) * TILE
+
+    runs = [whole(s[0] - 1, s[0] + 1)]
+    if step >= 3:
+        runs.append(whole(s[1] + 1, s[1] + step - 1))
+    runs += [whole(s[2], s[2] + 2 * step), whole(s[3], s[3] + step - 1),
+             (s[4] * TILE - 100, (s[4] + step + 1) * TILE + 7), ((tops - 1) * step * TILE, n)]
+    assert runs[0][0] > 0 and all(a < b for a, b in runs) and all(x[1] < y[0] for x, y in zip(runs, runs[1:]))
+    return runs
+
+
+def fence_layouts(n, step, tops, seed):
+    """(name, sorted keys, whether a value fills more than a staged group)."""
+    keys = sparse_keys(n, seed)
+    yield "distinct sparse keys", keys, False
+    keys = keys.copy()
+    runs = staged_runs(n, step, tops)
+    for a, b in runs:
+        keys[a:b] = keys[a]
+    yield "runs of whole tiles against the staged fences", keys, True
+    keys = keys.copy()
+    keys[0] = 0
+    keys[runs[-1][0]:] = U64_MAX
+    yield "the same with 0 and 2^64 - 1 at the ends", keys, True
+
+
+def aimed_queries(keys, starts, seed):
+    """For every tile (starts: its first record's index) its fence and the
+    record in front of it, each with - 1 and + 1; the first and last key, 0
+    and 2^64 - 1; 2000 keys with - 1 and + 1 and 1000 draws; shuffled."""
+    one = np.uint64(1)
+    rng = np.random.default_rng(seed)
+    f = keys[starts]
+    p = keys[starts[starts > 0] - 1]
+    hits = keys[rng.integers(0, keys.size, 2000)]
+    q = np.concatenate([f, f - one, f + one, p, p - one, p + one, hits, hits - one, hits + one,
+                        rng.integers(0, 1 << 63, 1000, dtype=np.int64).astype(np.uint64) * np.uint64(2) + one,
+                        np.array([keys[0], keys[-1], 0, U64_MAX], dtype=np.uint64)])
+    rng.shuffle(q)
+    return q
+
+
+# name -> (a, b, step, fences of the last staged group): a * kSearchTop + b tiles
+FENCE_TILES = {"top": (1, 0, 1, 1),            # every LDS slot used, the second level still empty
+               "top_plus_1": (1, 1, 2, 1),     # the smallest step > 1; the last group short, fend clamped to tiles
+               "2top_plus_2": (2, 2, 3, 1),    # a second level of 2 fences: both branches of its loop
+               "4top_plus_3": (4, 3, 5, 4)}    # a second level of 4 fences (3 in the last group): up to 3 probes
+LAST_TILE = {"full": lambda tiles: tiles * TILE, "short": lambda tiles: tiles * TILE - 1234,
+             "one_record": lambda tiles: (tiles - 1) * TILE + 1}
+
+
+@pytest.mark.parametrize("last_tile", list(LAST_TILE))
+@pytest.mark.parametrize("size", list(FENCE_TILES))
+@torch_first
+def test_two_level_fence_table(lsb_built, size, last_tile):
+    """Ranks of kSearchTop tiles and more: from kSearchTop + 1 on only every
+    step-th fence is staged and the fences between two staged ones are
+    searched too.  The sizes are derived from the kernel's constant and the
+    levels they reach are asserted, so another constant cannot turn this into
+    a test of one level."""
+    L = lsb_built
+    top = search_top()
+    a, b, want_step, want_last = FENCE_TILES[size]
+    tiles = a * top + b
+    step, tops, last = fence_levels(tiles, top)
+    assert (step, last) == (want_step, want_last) and tops <= top
+    assert tops == top if size == "top" else (step > 1 and last < step and (tops - 1) * step + last == tiles)
+    n = LAST_TILE[last_tile](tiles)
+    assert -(-n // TILE) == tiles
+    starts = np.arange(tiles, dtype=np.int64) * TILE
+    with L.World(n, ranks=1) as w:
+        for name, keys, long_runs in fence_layouts(n, step, tops, tiles):
+            q = aimed_queries(keys, starts, tiles + 1)
+            want = model(keys, q)
+            # the oracle: answers in every staged group that holds one (a group inside a run holds none), the
+            # last included; with the runs, a value that fills more than a staged group
+            ends = np.append(np.flatnonzero(keys[1:] != keys[:-1]) + 1, n)
+            holds = np.unique((ends - 1) // TILE // step)
+            ans = np.concatenate([want["left"], want["right"]])
+            assert np.array_equal(np.unique((ans[ans > 0] - 1) // TILE // step), holds) and holds[-1] == tops - 1, name
+            if long_runs:
+                assert (want["right"] - want["left"]).max() > step * TILE, name
+            else:
+                assert np.array_equal(holds, np.arange(tops)), name
+            w.copy_in(0, records(keys))
+            check_one_rank(w, keys, q, (name, tiles, n))
+
+
+@torch_first
+def test_two_level_fence_table_loopback(lsb_built):
+    """Two ranks of kSearchTop + 2 tiles each, the last one record short: each
+    rank's own fence table has two levels, and the ranks' answers add up,
+    also for a value that runs over the rank boundary."""
+    L = lsb_built
+    top = search_top()
+    P, per = 2, (top + 1) * TILE + 37
+    n = P * per - 1
+    tiles = -(-per // TILE)
+    assert -(-(per - 1) // TILE) == tiles  # the last rank's too
+    step, tops, last = fence_levels(tiles, top)
+    assert step == 2 and tops <= top and (tops - 1) * step + last == tiles
+    starts = np.concatenate([r * per + np.arange(tiles, dtype=np.int64) * TILE for r in range(P)])
+    sparse = sparse_keys(n, 11)
+    runs = sparse.copy()
+    over = (per - 3 * TILE - 100, per + (2 * step + 1) * TILE + 500)  # over the boundary, whole staged groups of both
+    spans = (staged_runs(per, step, tops)[:-1] + [over] +  # the first rank's last group belongs to `over`
+             [(per + x, per + y) for x, y in staged_runs(per - 1, step, tops)])
+    assert all(x[1] < y[0] for x, y in zip(spans, spans[1:])) and spans[-1][1] == n
+    for x, y in spans:
+        runs[x:y] = runs[x]
+    with L.World(n, ranks=P) as w:
+        assert w.per == per and w.here(P - 1) == per - 1
+        for name, keys in (("distinct sparse keys", sparse), ("runs, one over the rank boundary", runs)):
+            q = np.append(aimed_queries(keys, starts, 12), keys[per])
+            qt = column(q)
+            want = model(keys, q)
+            w.scatter_global(records(keys))
+            for side in SIDES:
+                assert np.array_equal(search_all_ranks(w, qt, side), want[side]), (name, side)
+        assert want["left"][-1] == over[0] < per < over[1] == want["right"][-1]  # the oracle sees the run on both ranks
+        assert min(per - over[0], over[1] - per) > step * TILE
+
+
+# ------------------------------------------------- 11. every key form at the kernel
+def form_bits(name):
+    """Distinct raw bit patterns of the type, zero-extended: 600 draws over
+    every byte, the integers' minimum, -1, 0, 1 and maximum, the floats' two
+    zeros, two infinities, NaNs of both signs with two payloads each (a quiet
+    and a signalling one), the smallest subnormals and the largest finite
+    values of both signs."""
+    kt, dt = KEYS[name]
+    width = 8 * np.dtype(dt).itemsize
+    mask, sign = (1 << width) - 1, 1 << (width - 1)
+    draws = np.random.default_rng(200 + kt).integers(0, 256, (600, 8), dtype=np.uint8).view(np.uint64).ravel()
+    if name in ("f32", "f64"):
+        inf, quiet = (0x7f800000, 0x00400000) if width == 32 else (0x7ff0000000000000, 0x0008000000000000)
+        special = [0, sign, inf, sign | inf, inf | quiet | 1, inf | 2, sign | inf | quiet | 1, sign | inf | 2,
+                   1, sign | 1, inf - 1, sign | (inf - 1)]
+    else:
+        special = [sign, mask, 0, 1, sign - 1, sign + 1, mask - 1]
+    return np.unique(np.concatenate([draws & np.uint64(mask), np.array(special, dtype=np.uint64)]))
+
+
+@pytest.mark.parametrize("descending", [False, True], ids=["ascending", "descending"])
+@pytest.mark.parametrize("name", list(KEYS))
+@torch_first
+def test_every_key_form(lsb_built, name, descending):
+    """k_search encodes the queries on the device from (key type, flags): all
+    12 forms against records whose keys are the model's encoding of typed
+    values, the specials of every type among them."""
+    import torch
+    L = lsb_built
+    kt, dt = KEYS[name]
+    n = 3 * TILE + 5
+    wide = np.dtype(dt).itemsize == 8
+    mask = U64_MAX if wide else np.uint64(0xFFFFFFFF)
+    one = np.uint64(1)
+    rng = np.random.default_rng(210 + kt)
+    pool = form_bits(name)
+    bits = np.concatenate([pool, rng.choice(pool, n - pool.size)])  # every value, with ties
+    keys = np.sort(model_encode(bits, kt, descending))
+    qbits = np.concatenate([pool, (pool + one) & mask, (pool - one) & mask,
+                            rng.integers(0, 256, (600, 8), dtype=np.uint8).view(np.uint64).ravel() & mask])
+    rng.shuffle(qbits)
+    want = model(keys, model_encode(qbits, kt, descending))
+    assert want["count"].max() > 1 and (want["count"] == 0).sum() > 100  # hits with ties, and misses
+    # the model's order is the type's: the values that compare, by value; NaNs at both ends, by sign
+    typed = bits.astype(np.uint64 if wide else np.uint32).view(dt)[np.argsort(model_encode(bits, kt, descending))]
+    if name in ("f32", "f64"):
+        assert np.isnan(typed[0]) and np.isnan(typed[-1]) and np.signbit(typed[0]) != descending
+        typed = typed[~np.isnan(typed)]
+    assert np.all(typed[1:] <= typed[:-1] if descending else typed[1:] >= typed[:-1])
+    assert typed[0] != typed[-1]
+    key_np = {"u64": np.int64, "u32": np.int32}.get(name, dt)  # uint columns travel as tensors of the same width
+    dq = torch.from_numpy(qbits.astype(np.uint64 if wide else np.uint32).view(key_np).copy()).cuda()
+    columns = [("", dq)]
+    if not wide:  # a column that starts 4 bytes into its allocation
+        room = torch.zeros(dq.numel() + 1, dtype=dq.dtype, device="cuda")
+        room[1:] = dq
+        columns.append(("4 bytes into its allocation", room[1:]))
+        assert room[1:].data_ptr() % 8 == 4
+    with L.World(n, ranks=1) as w:
+        w.copy_in(0, records(keys))
+        for what, col in columns:
+            assert np.array_equal(bits_of(host(col)), qbits)
+            for side in SIDES:
+                got = search(w, 0, col, side, key_type=kt, descending=descending)
+                assert np.array_equal(got, want[side]), (name, descending, side, what)
+
+
+# ------------------------------------------------- 12. COUNT's gallop at its ends
+@torch_first
+def test_count_gallop_ends(lsb_built):
+    """Runs of 2^j - 1, 2^j and 2^j + 1 records, j = 0..13, where the gallop's
+    last step and the binary search behind it end: inside the rank, on the
+    rank's last record, and from a tile's last record on."""
+    import torch
+    L = lsb_built
+    n = 3 * TILE + 5
+    lengths = sorted({r for j in range(14) for r in ((1 << j) - 1, 1 << j, (1 << j) + 1) if r > 0})
+    assert lengths[-1] == (1 << 13) + 1 and TILE - 1 + lengths[-1] <= n
+    base = np.arange(n, dtype=np.uint64) * np.uint64(8) + np.uint64(5)
+    one = np.uint64(1)
+    rng = np.random.default_rng(12)
+    with L.World(n, ranks=1) as w:
+        for r in lengths:
+            for what, a in (("inside the rank", 1001), ("up to the rank's last record", n - r),
+                            ("from a tile's last record", TILE - 1)):
+                keys = base.copy()
+                keys[a:a + r] = keys[a]
+                v = keys[a]
+                q = np.concatenate([np.array([v, v - one, v + one, keys[a - 1], keys[min(a + r, n - 1)], keys[0],
+                                              keys[-1], 0, U64_MAX], dtype=np.uint64), keys[::97], keys[::89] + one])
+                qt = column(q)
+                want = model(keys, q)["count"]
+                assert want[0] == r and want[1] == 0 and want[2] == 0
+                start = rng.integers(-(1 << 40), 1 << 40, q.size).astype(np.int64)
+                w.copy_in(0, records(keys))
+                assert np.array_equal(search(w, 0, qt, "count"), want), (r, what)
+                got = search(w, 0, qt, "count", add=True, out=torch.from_numpy(start.copy()).cuda())
+                assert np.array_equal(got, start + want), (r, what, "ADD")
