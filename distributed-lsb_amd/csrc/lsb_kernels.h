@@ -46,6 +46,8 @@ constexpr int kOsIpt = kTile / kOsBlock;
 constexpr int kOsSplitBlock = LSB_OS_SPLIT_BLOCK;
 constexpr int kOsSplitIpt = kTile / kOsSplitBlock;
 static_assert(kOsBlock % kBuckets == 0 && kOsBlock * kOsIpt == kTile, "onesweep tile shape");
+static_assert(kTile == kOsTile && kOsBlock == kOsWholeBlock && kOsSplitBlock == kOsHalvesBlock,
+              "kOsInstances (lsb_ostile.h) is written for these shapes");
 constexpr int kMaxChunks = 65536;             // upper bound on the chunk grid
 
 // A rank's `m` elements are cut into `num_chunks` contiguous chunks of
@@ -308,8 +310,10 @@ struct OnesweepExtra {
   // Packed -> Elem.
   bool pack_in = false, pack_out = false;
   // Records per tile of this pass's input and of the next pass's (0: kTile).
-  // Over kTile only in the combinations of os_pass_tiles_ok (lsb_ostile.h: a
-  // packed sort's passes), and only where onesweep_tile_fits.
+  // Over kTile only for a packed sort's passes, and only where
+  // onesweep_tile_fits.  The launch is refused unless kOsInstances
+  // (lsb_ostile.h) has a row for the request (os_select): a new tile size or
+  // form is one more row there, and the row is what builds its kernel.
   int tile = 0, next_tile = 0;
 };
 // The runtime's choice of OnesweepExtra::halves for a rank, from a digit's

@@ -27,6 +27,7 @@
 //     16-byte stores from consecutive lanes.
 #include "lsb_device.h"
 #include <type_traits>
+#include <utility>
 
 // Debug build (make debug, -DLSB_DEBUG): device-side bounds asserts on every
 // scattered store.  A failing assert prints and traps the kernel.
@@ -2490,192 +2491,71 @@ int onesweep_halves_for(const uint32_t* h, int64_t m) {
   return 1;
 }
 
+// The kernel of every row of kOsInstances (lsb_ostile.h), in the table's
+// order: naming them here is what instantiates them.  They share one type.
+using OsKernel = decltype(&k_onesweep<kOsBlock, kOsIpt, false, false, 1>);
+template <size_t I>
+constexpr OsKernel os_kernel() {
+  constexpr OsInstance r = kOsInstances[I];
+  return k_onesweep<r.block, r.ipt, r.next, r.c16, r.halves, r.seg, r.gather, r.rg, r.pin, r.pout, r.tn>;
+}
+template <size_t... I>
+const OsKernel* os_kernels(std::index_sequence<I...>) {
+  static const OsKernel k[] = {os_kernel<I>()...};
+  return k;
+}
+
 hipError_t launch_onesweep(const Elem* in, Elem* out, int64_t m, int shift, int next_shift,
                            const uint32_t* sub_hist, uint32_t* next_hist, uint32_t* status,
                            uint32_t* tile_ctr, uint32_t epoch, uint32_t* err, int grid,
                            hipStream_t s, OnesweepExtra extra) {
   if (m <= 0) return hipSuccess;
-  if (m > kOnesweepMaxElems || epoch == 0 || epoch >= (1u << 31) || shift < 0 || shift > 56 ||
-      next_shift > 56 || (extra.halves != 1 && extra.halves != 2))
+  // The request: its ranges and the pointers its form needs, here; the form
+  // itself, the tile sizes and "nothing else set", in os_select.
+  if (m > kOnesweepMaxElems || epoch == 0 || epoch >= (1u << 31) || shift < 0 || shift > 56 || next_shift > 56)
     return hipErrorInvalidValue;
-  hipError_t e = hipMemsetAsync(tile_ctr, 0, sizeof(uint32_t) * kSub, s);
-  if (e != hipSuccess) return e;
   const int rm = extra.region_mode;
-  const RegionPass rp = extra.region ? *extra.region : RegionPass();
-  // Records per tile of this pass and of the next (over kTile: the passes of
-  // a packed sort that read packed records, lsb_kernels.h): the instances
-  // built are os_pass_tiles_ok's table (lsb_ostile.h).
-  const int T = extra.tile ? extra.tile : kTile, TN = extra.next_tile ? extra.next_tile : kTile;
-  if (rm < 0 || rm > 2 || (rm != 0 && (!extra.region || rp.cap <= 0 || rp.cap % kTile != 0 || (rm == 2 && rp.cap % T != 0) ||
-                                       rp.cap * kRegions < m || !rp.counts)))
+  const RegionPass rp = rm != 0 && extra.region ? *extra.region : RegionPass();
+  // Records per tile of this pass (over kTile: a packed sort's passes, lsb_kernels.h).
+  const int T = extra.tile ? extra.tile : kTile;
+  if (rm != 0 && (rp.cap <= 0 || rp.cap % kTile != 0 || (rm == 2 && rp.cap % T != 0) || rp.cap * kRegions < m || !rp.counts))
     return hipErrorInvalidValue;
-  const OsPassKind kind = rm == 1                                ? kOsPassFirst
-                          : rm == 2                              ? kOsPassLayout
-                          : extra.pack_in && next_shift >= 0     ? kOsPassMiddle
-                          : extra.pack_in                        ? kOsPassLast
-                                                                 : kOsPassOther;
-  if (!os_pass_tiles_ok(kind, T, next_shift >= 0 ? TN : kTile, kTile) ||
-      ((T != kTile || TN != kTile) && !extra.pack_in && !(rm == 1 && extra.pack_out)) ||
-      (next_shift >= 0 && rm != 1 && !onesweep_tile_fits(T, TN, m)))
-    return hipErrorInvalidValue;
+  // The first pass reports overflowing regions, and wide values when it packs.
+  if (rm == 1 && (!rp.ovf || (extra.pack_out && !rp.wide))) return hipErrorInvalidValue;
+  if (extra.probe && !next_hist) return hipErrorInvalidValue;
+  if (extra.seg && (!extra.seg->base || !extra.seg->err)) return hipErrorInvalidValue;
+  auto* c16 = reinterpret_cast<unsigned long long*>(extra.count16);
+  const OsRequest q = {m, shift, next_shift, rm, extra.pack_in, extra.pack_out,
+                       /*count16, seg, gather, probe, totals*/ c16 != nullptr, extra.seg != nullptr,
+                       extra.gather != nullptr, extra.probe, extra.totals != nullptr, extra.halves, extra.tile,
+                       extra.next_tile};
+  const int row = os_select(q);
+  if (row < 0) return hipErrorInvalidValue;
+  const OsInstance& k = kOsInstances[row];
+  // What the instance accumulates into is zeroed first.
+  hipError_t e = hipMemsetAsync(tile_ctr, 0, sizeof(uint32_t) * kSub, s);
+  if (e == hipSuccess && k.next) e = hipMemsetAsync(next_hist, 0, sizeof(uint32_t) * kSub * kBuckets, s);
+  if (e == hipSuccess && k.c16) e = hipMemsetAsync(c16, 0, sizeof(uint64_t) * 65536, s);
+  if (e == hipSuccess && k.rg == 1) e = hipMemsetAsync(rp.counts, 0, sizeof(uint32_t) * kRegions, s);
+  if (e == hipSuccess && k.rg == 1) e = hipMemsetAsync(rp.ovf, 0, sizeof(uint32_t), s);
+  if (e == hipSuccess && k.rg == 1 && k.pout) e = hipMemsetAsync(rp.wide, 0, sizeof(uint32_t), s);
+  if (e != hipSuccess) return e;
   // Tiles of the input: the regional layout's slots for its reading pass.
   const int64_t TT = rm == 2 ? os_rows_track2(rp.cap, T, kRegions) : (m + T - 1) / T;
-  auto* c16 = reinterpret_cast<unsigned long long*>(extra.count16);
-  const bool gat = extra.gather != nullptr;
-  // The split stage only for the plain and next-digit forms, never gathered
-  // (its gathered instances spill: 160-236 B per lane at 168 VGPRs; a
-  // gathered pass takes the whole stage, lsb_exchange.cpp local_pass_os).
-  if (extra.halves == 2 && gat) return hipErrorInvalidValue;
-  const bool split = extra.halves == 2 && c16 == nullptr;
   // Persistent grid (`grid` = 2 workgroups per CU; 3 with the split stage),
   // a multiple of the XCD count; no more than the tiles.
-  int64_t g = split ? (int64_t)grid * 3 / 2 : grid;
+  int64_t g = k.halves == 2 ? (int64_t)grid * 3 / 2 : grid;
   if (g < kSub) g = kSub;
   if (g > (TT + kSub - 1) / kSub * kSub) g = (TT + kSub - 1) / kSub * kSub;
-  const dim3 gd((unsigned)g), bd(split ? kOsSplitBlock : kOsBlock);
-  uint32_t* st = status;
+  const dim3 gd((unsigned)g), bd(k.block);
   const GatherSrc gsrc = extra.gather ? *extra.gather : GatherSrc();
-  // One launch of the instance, gathered or not.
-  auto go = [&](auto kplain, auto kgather, int nshift, uint32_t* nhist, unsigned long long* cnt16,
-                SegPass sp) {
-    hipLaunchKernelGGL(gat ? kgather : kplain, gd, bd, 0, s, in, out, m, shift, nshift, sub_hist, nhist,
-                       st, tile_ctr, epoch, err, extra.totals, cnt16, sp, gsrc, RegionPass());
-  };
-  if (rm != 0) {
-    // The regional first pass (rm = 1) and the pass that reads its layout
-    // (rm = 2): whole stage, no 16-bit counts, totals, segments or gathering.
-    if (c16 || extra.halves != 1 || extra.seg || gat || extra.probe || extra.totals) return hipErrorInvalidValue;
-    if (rm == 1 && (next_shift < 0 || !rp.ovf)) return hipErrorInvalidValue;
-    // Packed records: the first pass packs (and reports wide values), the
-    // pass that reads its layout carries them on to a next-counting pass.
-    if (rm == 1 ? (extra.pack_in || (extra.pack_out && !rp.wide))
-                : (extra.pack_in != extra.pack_out || (extra.pack_in && next_shift < 0)))
-      return hipErrorInvalidValue;
-    if (next_shift >= 0) {
-      e = hipMemsetAsync(next_hist, 0, sizeof(uint32_t) * kSub * kBuckets, s);
-      if (e != hipSuccess) return e;
-    }
-    if (rm == 1) {
-      e = hipMemsetAsync(rp.counts, 0, sizeof(uint32_t) * kRegions, s);
-      if (e == hipSuccess) e = hipMemsetAsync(rp.ovf, 0, sizeof(uint32_t), s);
-      if (e == hipSuccess && extra.pack_out) e = hipMemsetAsync(rp.wide, 0, sizeof(uint32_t), s);
-      if (e != hipSuccess) return e;
-      if (extra.pack_out && T == kOsTile10)  // the packing first pass in large tiles
-        hipLaunchKernelGGL((k_onesweep<kOsBlock, 10, true, false, 1, false, false, 1, false, true>), gd, bd, 0, s,
-                           in, out, m, shift, next_shift, sub_hist, next_hist, st, tile_ctr, epoch, err, nullptr,
-                           nullptr, SegPass(), gsrc, rp);
-      else if (extra.pack_out)
-        hipLaunchKernelGGL((k_onesweep<kOsBlock, kOsIpt, true, false, 1, false, false, 1, false, true>), gd, bd, 0, s,
-                           in, out, m, shift, next_shift, sub_hist, next_hist, st, tile_ctr, epoch, err, nullptr,
-                           nullptr, SegPass(), gsrc, rp);
-      else
-        hipLaunchKernelGGL((k_onesweep<kOsBlock, kOsIpt, true, false, 1, false, false, 1>), gd, bd, 0, s, in, out,
-                           m, shift, next_shift, sub_hist, next_hist, st, tile_ctr, epoch, err, nullptr, nullptr,
-                           SegPass(), gsrc, rp);
-    } else if (next_shift >= 0 && extra.pack_in) {
-      if (T == kOsTile10)  // the layout in large tiles (cap a multiple of them); TN = T
-        hipLaunchKernelGGL((k_onesweep<kOsBlock, 10, true, false, 1, false, false, 2, true, true, kOsTile10>),
-                           gd, bd, 0, s, in, out, m, shift, next_shift, sub_hist, next_hist, st, tile_ctr, epoch, err,
-                           nullptr, nullptr, SegPass(), gsrc, rp);
-      else if (TN == kOsTile10)
-        hipLaunchKernelGGL((k_onesweep<kOsBlock, kOsIpt, true, false, 1, false, false, 2, true, true, kOsTile10>),
-                           gd, bd, 0, s, in, out, m, shift, next_shift, sub_hist, next_hist, st, tile_ctr, epoch, err,
-                           nullptr, nullptr, SegPass(), gsrc, rp);
-      else if (TN == kOsTile9)
-        hipLaunchKernelGGL((k_onesweep<kOsBlock, kOsIpt, true, false, 1, false, false, 2, true, true, kOsTile9>),
-                           gd, bd, 0, s, in, out, m, shift, next_shift, sub_hist, next_hist, st, tile_ctr, epoch, err,
-                           nullptr, nullptr, SegPass(), gsrc, rp);
-      else
-        hipLaunchKernelGGL((k_onesweep<kOsBlock, kOsIpt, true, false, 1, false, false, 2, true, true>), gd, bd, 0, s,
-                           in, out, m, shift, next_shift, sub_hist, next_hist, st, tile_ctr, epoch, err, nullptr,
-                           nullptr, SegPass(), gsrc, rp);
-    } else if (next_shift >= 0) {
-      hipLaunchKernelGGL((k_onesweep<kOsBlock, kOsIpt, true, false, 1, false, false, 2>), gd, bd, 0, s, in, out,
-                         m, shift, next_shift, sub_hist, next_hist, st, tile_ctr, epoch, err, nullptr, nullptr,
-                         SegPass(), gsrc, rp);
-    } else {
-      hipLaunchKernelGGL((k_onesweep<kOsBlock, kOsIpt, false, false, 1, false, false, 2>), gd, bd, 0, s, in, out,
-                         m, shift, 0, sub_hist, nullptr, st, tile_ctr, epoch, err, nullptr, nullptr, SegPass(),
-                         gsrc, rp);
-    }
-  } else if (extra.pack_in) {
-    // A later pass of a packed sort: Packed -> Packed counting the next
-    // digit, or the last pass Packed -> Elem.  Whole stage, nothing else.
-    if (c16 || extra.halves != 1 || extra.seg || gat || extra.probe || extra.totals ||
-        extra.pack_out != (next_shift >= 0))
-      return hipErrorInvalidValue;
-    if (next_shift >= 0) {
-      e = hipMemsetAsync(next_hist, 0, sizeof(uint32_t) * kSub * kBuckets, s);
-      if (e != hipSuccess) return e;
-      // A middle pass of IPT records per thread; TN: kTile at the seam before
-      // the last pass, else its own size.
-      auto big = [&](auto ipt, auto tn) {
-        hipLaunchKernelGGL(
-            (k_onesweep<kOsBlock, decltype(ipt)::value, true, false, 1, false, false, 0, true, true, decltype(tn)::value>),
-            gd, bd, 0, s, in, out, m, shift, next_shift, sub_hist, next_hist, st, tile_ctr, epoch, err, nullptr,
-            nullptr, SegPass(), gsrc, RegionPass());
-      };
-      using I9 = std::integral_constant<int, 9>;
-      using I10 = std::integral_constant<int, 10>;
-      if (T == kOsTile10 && TN == T) big(I10(), std::integral_constant<int, kOsTile10>());
-      else if (T == kOsTile10) big(I10(), std::integral_constant<int, kTile>());
-      else if (T == kOsTile9 && TN == T) big(I9(), std::integral_constant<int, kOsTile9>());
-      else if (T == kOsTile9) big(I9(), std::integral_constant<int, kTile>());
-      else
-        hipLaunchKernelGGL((k_onesweep<kOsBlock, kOsIpt, true, false, 1, false, false, 0, true, true>), gd, bd, 0, s,
-                           in, out, m, shift, next_shift, sub_hist, next_hist, st, tile_ctr, epoch, err, nullptr,
-                           nullptr, SegPass(), gsrc, RegionPass());
-    } else if (T == kOsTile10) {  // the last pass in large tiles: values widened at the write-out
-      hipLaunchKernelGGL((k_onesweep<kOsBlock, 10, false, false, 1, false, false, 0, true, false>), gd, bd, 0, s,
-                         in, out, m, shift, 0, sub_hist, nullptr, st, tile_ctr, epoch, err, nullptr, nullptr,
-                         SegPass(), gsrc, RegionPass());
-    } else {
-      hipLaunchKernelGGL((k_onesweep<kOsBlock, kOsIpt, false, false, 1, false, false, 0, true, false>), gd, bd, 0, s,
-                         in, out, m, shift, 0, sub_hist, nullptr, st, tile_ctr, epoch, err, nullptr, nullptr,
-                         SegPass(), gsrc, RegionPass());
-    }
-  } else if (extra.pack_out) {
-    return hipErrorInvalidValue;  // only the regional first pass packs
-  } else if (extra.probe) {
-    // The placement probe: a pass counting the next digit (the sort's usual
-    // instance), whole stage, under its own name.
-    if (next_shift < 0 || !next_hist || c16 || extra.halves != 1 || extra.seg || gat) return hipErrorInvalidValue;
-    e = hipMemsetAsync(next_hist, 0, sizeof(uint32_t) * kSub * kBuckets, s);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_onesweep_probe, gd, bd, 0, s, in, out, m, shift, next_shift, sub_hist, next_hist, st,
+  if (extra.probe)  // the plain next-counting row's body under its own name
+    hipLaunchKernelGGL(k_onesweep_probe, gd, bd, 0, s, in, out, m, shift, next_shift, sub_hist, next_hist, status,
                        tile_ctr, epoch, err, nullptr, nullptr, SegPass(), gsrc);
-  } else if (extra.seg) {
-    // The hybrid's last pass: no next digit, no 16-bit counts, whole stage.
-    if (next_shift >= 0 || c16 || extra.halves != 1 || !extra.seg->base ||
-        !extra.seg->err || gat)
-      return hipErrorInvalidValue;
-    hipLaunchKernelGGL((k_onesweep<kOsBlock, kOsIpt, false, false, 1, true>), gd, bd, 0, s, in, out, m,
-                       shift, 0, sub_hist, nullptr, st, tile_ctr, epoch, err, extra.totals, nullptr,
-                       *extra.seg, gsrc, RegionPass());
-  } else if (c16) {
-    // The 16-bit counts need the low byte below this digit, and no next
-    // digit: the exchange follows this pass.
-    if (shift < 8 || next_shift >= 0) return hipErrorInvalidValue;
-    e = hipMemsetAsync(c16, 0, sizeof(uint64_t) * 65536, s);
-    if (e != hipSuccess) return e;
-    go(k_onesweep<kOsBlock, kOsIpt, false, true, 1>, k_onesweep<kOsBlock, kOsIpt, false, true, 1, false, true>,
-       0, nullptr, c16, SegPass());
-  } else if (next_shift >= 0) {
-    e = hipMemsetAsync(next_hist, 0, sizeof(uint32_t) * kSub * kBuckets, s);
-    if (e != hipSuccess) return e;
-    if (split)  // never gathered (checked above)
-      go(k_onesweep<kOsSplitBlock, kOsSplitIpt, true, false, 2>,
-         k_onesweep<kOsSplitBlock, kOsSplitIpt, true, false, 2>, next_shift, next_hist, nullptr, SegPass());
-    else
-      go(k_onesweep<kOsBlock, kOsIpt, true, false, 1>, k_onesweep<kOsBlock, kOsIpt, true, false, 1, false, true>,
-         next_shift, next_hist, nullptr, SegPass());
-  } else if (split) {  // never gathered (checked above)
-    go(k_onesweep<kOsSplitBlock, kOsSplitIpt, false, false, 2>,
-       k_onesweep<kOsSplitBlock, kOsSplitIpt, false, false, 2>, 0, nullptr, nullptr, SegPass());
-  } else {
-    go(k_onesweep<kOsBlock, kOsIpt, false, false, 1>, k_onesweep<kOsBlock, kOsIpt, false, false, 1, false, true>,
-       0, nullptr, nullptr, SegPass());
-  }
+  else
+    hipLaunchKernelGGL(os_kernels(std::make_index_sequence<kOsInstanceCount>())[row], gd, bd, 0, s, in, out, m, shift,
+                       k.next ? next_shift : 0, sub_hist, k.next ? next_hist : nullptr, status, tile_ctr, epoch, err,
+                       extra.totals, c16, extra.seg ? *extra.seg : SegPass(), gsrc, rp);
   return hipGetLastError();
 }
 
@@ -2686,36 +2566,16 @@ hipError_t launch_place(const Elem* src, Elem* out, int64_t out_len, int64_t k0,
   if (nbuckets != 256 && nbuckets != 65536) return hipErrorInvalidValue;
   if (k0 < 0 || k0 + count > out_len) return hipErrorInvalidValue;
   const uint32_t mask = (uint32_t)nbuckets - 1;
-  const bool lds = nbuckets <= kPlaceLdsBuckets;
-  if (next_shift >= 0) {
-    if (next_shift > 56 || !next_hist || out_len > kOnesweepMaxElems) return hipErrorInvalidValue;
-    // Fewer, longer-lived workgroups: each flushes its 8 x 256 counters once.
-    const dim3 grid(grid_for(count, kPlaceBlock * kPlaceIpt, kPlaceNextGrid));
-    if (!store) {
-      if (lds)
-        hipLaunchKernelGGL((k_place<true, true, false>), grid, dim3(kPlaceBlock), 0, s, src, out, k0,
-                           count, shift, mask, off_row, out_len, next_shift, next_hist, skew ? 1u : 0u);
-      else
-        hipLaunchKernelGGL((k_place<false, true, false>), grid, dim3(kPlaceBlock), 0, s, src, out, k0,
-                           count, shift, mask, off_row, out_len, next_shift, next_hist, skew ? 1u : 0u);
-      return hipGetLastError();
-    }
-    if (lds)
-      hipLaunchKernelGGL((k_place<true, true>), grid, dim3(kPlaceBlock), 0, s, src, out, k0, count,
-                         shift, mask, off_row, out_len, next_shift, next_hist, skew ? 1u : 0u);
-    else
-      hipLaunchKernelGGL((k_place<false, true>), grid, dim3(kPlaceBlock), 0, s, src, out, k0, count,
-                         shift, mask, off_row, out_len, next_shift, next_hist, skew ? 1u : 0u);
-    return hipGetLastError();
-  }
-  if (!store) return hipErrorInvalidValue;  // nothing to count
-  const dim3 grid(grid_for(count, kPlaceBlock * kPlaceIpt, 4096));
-  if (lds)
-    hipLaunchKernelGGL((k_place<true, false>), grid, dim3(kPlaceBlock), 0, s, src, out, k0, count,
-                       shift, mask, off_row, out_len, 0, nullptr, 0u);
-  else
-    hipLaunchKernelGGL((k_place<false, false>), grid, dim3(kPlaceBlock), 0, s, src, out, k0, count,
-                       shift, mask, off_row, out_len, 0, nullptr, 0u);
+  const bool lds = nbuckets <= kPlaceLdsBuckets, next = next_shift >= 0;
+  if (next && (next_shift > 56 || !next_hist || out_len > kOnesweepMaxElems)) return hipErrorInvalidValue;
+  if (!next && !store) return hipErrorInvalidValue;  // nothing to count
+  const auto k = !next   ? (lds ? k_place<true, false> : k_place<false, false>)
+                 : store ? (lds ? k_place<true, true> : k_place<false, true>)
+                         : (lds ? k_place<true, true, false> : k_place<false, true, false>);
+  // Counting the next digit: fewer, longer-lived workgroups, each flushes its 8 x 256 counters once.
+  const dim3 grid(grid_for(count, kPlaceBlock * kPlaceIpt, next ? kPlaceNextGrid : 4096));
+  hipLaunchKernelGGL(k, grid, dim3(kPlaceBlock), 0, s, src, out, k0, count, shift, mask, off_row, out_len,
+                     next ? next_shift : 0, next ? next_hist : nullptr, next && skew ? 1u : 0u);
   return hipGetLastError();
 }
 

@@ -1,8 +1,9 @@
 // k_onesweep's tile geometry where passes of different tile sizes meet: the
 // sub-arrays a pass counts the next digit by, when a larger tile applies, and
-// which look-back rows to refill.  Plain arithmetic, shared by the kernels
-// (lsb_kernels.hip), the runtime (lsb_passes.cpp) and the host checks
-// (tools/host_asan.cpp): no HIP types.
+// which look-back rows to refill; and the table of the instances that are
+// built.  Plain arithmetic, shared by the kernels (lsb_kernels.hip), the
+// runtime (lsb_passes.cpp) and the host checks (tools/host_asan.cpp,
+// tools/edgetile_host.cpp): no HIP types.
 #pragma once
 #include <stdint.h>
 
@@ -82,20 +83,142 @@ LSB_HD inline unsigned os_edge_applies(int64_t m, int64_t cap, unsigned setting,
   if (cap <= 0 || cap % big != 0) e &= ~kOsEdgeLayout;
   return e;
 }
-// The kinds of pass launch_onesweep tells apart by tile size, and the
-// (kind, t, tn) combinations it has instances for: t records per tile, the
-// next pass's tn (ignored by a pass that counts no next digit).
+// The passes of a sort that differ in tile size: a packed sort's first pass
+// (into the regional layout), the pass that reads the layout, its middle
+// passes (Packed -> Packed) and its last; every other pass is kOsPassOther.
 enum OsPassKind { kOsPassOther = 0, kOsPassFirst, kOsPassLayout, kOsPassMiddle, kOsPassLast };
-LSB_HD inline bool os_pass_tiles_ok(OsPassKind kind, int t, int tn, int small) {
-  const bool any_t = t == small || t == 4608 || t == kOsEdgeTile;
-  const bool any_tn = tn == small || tn == 4608 || tn == kOsEdgeTile;
-  switch (kind) {
-    case kOsPassFirst: return (t == small || t == kOsEdgeTile) && any_tn;  // regions: tn does not enter its counts
-    case kOsPassLayout: return (t == small && any_tn) || (t == kOsEdgeTile && tn == kOsEdgeTile);
-    case kOsPassMiddle: return any_t && (tn == t || tn == small);
-    case kOsPassLast: return t == small || t == kOsEdgeTile;
-    default: return t == small && tn == small;
-  }
+// Records per tile of one pass of a sort of m records whose other passes take
+// `small`: `packed_tile` (the context's setting) for the middle passes of a
+// packed sort where it fits, and for the edge passes where os_edge_applies
+// (cap: slots per region of the layout, 0 without one) and the context's
+// `edge_tiles` say so too.
+LSB_HD inline int os_pass_tile(OsPassKind pass, bool packed, int64_t m, int64_t cap, int packed_tile,
+                               unsigned edge_tiles, int small) {
+  if (pass == kOsPassOther || !packed || !os_big_applies(m, packed_tile, small)) return small;
+  if (pass == kOsPassMiddle) return packed_tile;
+  const unsigned bit = pass == kOsPassFirst ? kOsEdgeFirst : pass == kOsPassLayout ? kOsEdgeLayout : kOsEdgeLast;
+  return os_edge_applies(m, cap, edge_tiles, packed_tile, small) & bit ? packed_tile : small;
+}
+
+// Every k_onesweep instance that is built, one row per instantiation, by the
+// kernel's template arguments.  This is the only list: lsb_kernels.hip
+// instantiates the kernel of every row (adding a row is what builds it), and
+// launch_onesweep launches the row os_select picks.
+constexpr int kOsTile = 4096;                             // == kTile (lsb_kernels.h)
+constexpr int kOsWholeBlock = 512, kOsHalvesBlock = 256;  // threads: the whole stage, the split stage
+struct OsInstance {
+  int block, ipt;  // block x ipt records per tile
+  bool next, c16;
+  int halves;
+  bool seg, gather;
+  int rg;
+  bool pin, pout;
+  int tn;  // the next pass's records per tile (its own where no next digit is counted, and for rg = 1)
+};
+constexpr bool operator==(const OsInstance& a, const OsInstance& b) {
+  return a.block == b.block && a.ipt == b.ipt && a.next == b.next && a.c16 == b.c16 && a.halves == b.halves &&
+         a.seg == b.seg && a.gather == b.gather && a.rg == b.rg && a.pin == b.pin && a.pout == b.pout && a.tn == b.tn;
+}
+constexpr OsInstance kOsInstances[] = {
+    // Whole records, dense input: plain or gathered, the next digit or the
+    // 16-bit counts, the split stage, the hybrid's last pass.
+    {512, 8, false, false, 1, false, false, 0, false, false, 4096},
+    {512, 8, false, false, 1, false, true, 0, false, false, 4096},
+    {512, 8, true, false, 1, false, false, 0, false, false, 4096},  // the placement probe runs this one's body
+    {512, 8, true, false, 1, false, true, 0, false, false, 4096},
+    {512, 8, false, true, 1, false, false, 0, false, false, 4096},
+    {512, 8, false, true, 1, false, true, 0, false, false, 4096},
+    {256, 16, false, false, 2, false, false, 0, false, false, 4096},
+    {256, 16, true, false, 2, false, false, 0, false, false, 4096},
+    {512, 8, false, false, 1, true, false, 0, false, false, 4096},
+    // The first pass into the regional layout: whole records, packing, packing in large tiles.
+    {512, 8, true, false, 1, false, false, 1, false, false, 4096},
+    {512, 8, true, false, 1, false, false, 1, false, true, 4096},
+    {512, 10, true, false, 1, false, false, 1, false, true, 5120},
+    // The pass that reads the layout: whole records (last or not), packed
+    // before a pass of each tile size, packed in large tiles.
+    {512, 8, false, false, 1, false, false, 2, false, false, 4096},
+    {512, 8, true, false, 1, false, false, 2, false, false, 4096},
+    {512, 8, true, false, 1, false, false, 2, true, true, 4096},
+    {512, 8, true, false, 1, false, false, 2, true, true, 4608},
+    {512, 8, true, false, 1, false, false, 2, true, true, 5120},
+    {512, 10, true, false, 1, false, false, 2, true, true, 5120},
+    // A packed sort's middle passes: before a pass of their own tile size, or of 4096.
+    {512, 8, true, false, 1, false, false, 0, true, true, 4096},
+    {512, 9, true, false, 1, false, false, 0, true, true, 4608},
+    {512, 9, true, false, 1, false, false, 0, true, true, 4096},
+    {512, 10, true, false, 1, false, false, 0, true, true, 5120},
+    {512, 10, true, false, 1, false, false, 0, true, true, 4096},
+    // A packed sort's last pass (Packed -> Elem).
+    {512, 8, false, false, 1, false, false, 0, true, false, 4096},
+    {512, 10, false, false, 1, false, false, 0, true, false, 5120},
+};
+constexpr int kOsInstanceCount = (int)(sizeof(kOsInstances) / sizeof(kOsInstances[0]));
+constexpr int os_instance_tile(const OsInstance& r) { return r.block * r.ipt; }
+constexpr OsPassKind os_instance_kind(const OsInstance& r) {
+  return r.rg == 1 ? kOsPassFirst : r.rg == 2 ? kOsPassLayout : !r.pin ? kOsPassOther : r.next ? kOsPassMiddle : kOsPassLast;
+}
+// Some instance takes t records per tile.
+inline bool os_tile_built(int t) {
+  for (const OsInstance& r : kOsInstances)
+    if (os_instance_tile(r) == t) return true;
+  return false;
+}
+// A pass of that kind with t records per tile before one of tn has an
+// instance (tn: ignored by the last pass, which counts no next digit; any
+// built size for the first, whose counts are per region whatever tile reads
+// them).  Only at small = kOsTile: the table is built for no other.
+inline bool os_pass_tiles_ok(OsPassKind kind, int t, int tn, int small) {
+  if (small != kOsTile) return false;
+  for (const OsInstance& r : kOsInstances)
+    if (os_instance_kind(r) == kind && os_instance_tile(r) == t &&
+        (kind == kOsPassLast || (kind == kOsPassFirst ? os_tile_built(tn) : r.tn == tn)))
+      return true;
+  return false;
+}
+
+// A launch_onesweep request in plain terms (OnesweepExtra's pointers as
+// "set or not"; tile, next_tile: 0 = kOsTile), and the row of kOsInstances
+// that serves it: -1 when the request is refused or no instance is built.
+struct OsRequest {
+  int64_t m = 0;
+  int shift = 0, next_shift = -1;
+  int region_mode = 0;
+  bool pack_in = false, pack_out = false;
+  bool count16 = false, seg = false, gather = false, probe = false, totals = false;
+  int halves = 1;
+  int tile = 0, next_tile = 0;
+};
+inline int os_select(const OsRequest& q) {
+  const int rm = q.region_mode;
+  const bool next = q.next_shift >= 0;
+  const int T = q.tile ? q.tile : kOsTile, TN = q.next_tile ? q.next_tile : kOsTile;
+  if (rm < 0 || rm > 2 || (q.halves != 1 && q.halves != 2)) return -1;
+  // Tiles over kOsTile for packed records only; the first pass's next tile
+  // does not enter its instance, so it is checked here.
+  if ((T != kOsTile || TN != kOsTile) && !q.pack_in && !(rm == 1 && q.pack_out)) return -1;
+  if (rm == 1 && !os_tile_built(TN)) return -1;
+  // The seam to the next pass (the first pass writes regions, which no run crosses).
+  if (next && rm != 1 && !os_tile_fits(T, TN, q.m)) return -1;
+  // A regional or packed pass: whole stage, nothing else set.
+  if ((rm != 0 || q.pack_in) && (q.count16 || q.halves != 1 || q.seg || q.gather || q.probe || q.totals)) return -1;
+  // The placement probe: the plain pass counting the next digit, whole stage.
+  if (q.probe && (!next || q.count16 || q.halves != 1 || q.seg || q.gather)) return -1;
+  // The 16-bit counts need the low byte below this digit.
+  if (q.count16 && q.shift < 8) return -1;
+  // The split stage only for the plain and next-digit forms, never gathered
+  // (its gathered instances spill: 160-236 B per lane at 168 VGPRs; a
+  // gathered pass takes the whole stage, lsb_exchange.cpp local_pass_os), and
+  // not with the 16-bit counts, which run the whole stage.
+  if (q.halves == 2 && q.gather) return -1;
+  const bool split = q.halves == 2 && !q.count16;
+  const int block = split ? kOsHalvesBlock : kOsWholeBlock;
+  if (T % block != 0) return -1;
+  const OsInstance want = {block, T / block, next, q.count16, split ? 2 : 1, q.seg, q.gather,
+                           rm,    q.pack_in, q.pack_out, next && rm != 1 ? TN : T};
+  for (int i = 0; i < kOsInstanceCount; ++i)
+    if (kOsInstances[i] == want) return i;
+  return -1;
 }
 // Look-back rows a launch writes: the first track's, over the m records, and
 // the second track's (the pass that reads the regional layout), over the

@@ -240,19 +240,17 @@ int onesweep_digits(lsb_ctx* c, Rank& r, const std::vector<int>& digits, int* pa
   uint32_t* hist[2] = {r.os_hist, r.os_hist + lsb::kOnesweepSubs * lsb::kBuckets};
   // A packed sort's middle passes (Packed -> Packed, after the pass that
   // reads the regional layout and before the last) take the context's large
-  // tile where it fits (lsb::onesweep_big_applies); the pass before one
-  // counts the next digit by that size.
-  // The edge passes (the one that reads the regional layout, the last one)
-  // take it as well where lsb::os_edge_applies and the context's setting say.
-  const int big = packed && lsb::onesweep_big_applies(r.here, c->packed_tile) ? c->packed_tile : 0;
-  const unsigned edge = lsb::os_edge_applies(r.here, rp ? rp->cap : 0, c->edge_tiles, big, lsb::kTile);
+  // tile where it fits, and the edge passes (the one that reads the regional
+  // layout, the last one) take it as well where the context's setting says
+  // (lsb::os_pass_tile); the pass before one counts the next digit by that size.
   auto middle = [&](size_t i) { return packed && i > from && i + 1 < digits.size(); };
   auto tile_of = [&](size_t i) -> int {
     if (i >= digits.size()) return 0;
-    if (middle(i)) return big;
-    if (packed && rp && i == from) return edge & lsb::kOsEdgeLayout ? big : 0;
-    if (packed && i > from) return edge & lsb::kOsEdgeLast ? big : 0;  // the last pass
-    return 0;
+    const lsb::OsPassKind pass = middle(i)                   ? lsb::kOsPassMiddle
+                                 : packed && rp && i == from ? lsb::kOsPassLayout
+                                 : packed && i > from        ? lsb::kOsPassLast
+                                                             : lsb::kOsPassOther;
+    return lsb::os_pass_tile(pass, packed, r.here, rp ? rp->cap : 0, c->packed_tile, c->edge_tiles, lsb::kTile);
   };
   for (size_t i = from; i < digits.size(); ++i) {
     const int shift = digits[i] * lsb::kDigitBits;
@@ -283,7 +281,7 @@ int onesweep_digits(lsb_ctx* c, Rank& r, const std::vector<int>& digits, int* pa
       return rc;
     }
     ++*passes;
-    if (middle(i)) c->last_packed_tile = big ? big : lsb::kTile;
+    if (middle(i)) c->last_packed_tile = x.tile;
     if (disarm) *disarm = false;
   }
   return LSB_OK;
@@ -372,9 +370,8 @@ int region_first(lsb_ctx* c, Rank& r, int shift, int next_shift, int* passes, bo
   x.region_mode = 1;
   x.pack_out = pack;
   // A packed sort's first pass takes the large tile with its middle passes
-  // (lsb::os_edge_applies, as onesweep_digits decides for the other two).
-  const int big = pack && lsb::onesweep_big_applies(r.here, c->packed_tile) ? c->packed_tile : 0;
-  if (lsb::os_edge_applies(r.here, rp.cap, c->edge_tiles, big, lsb::kTile) & lsb::kOsEdgeFirst) x.tile = big;
+  // (lsb::os_pass_tile, as onesweep_digits asks for the other passes).
+  x.tile = lsb::os_pass_tile(lsb::kOsPassFirst, pack, r.here, rp.cap, c->packed_tile, c->edge_tiles, lsb::kTile);
   LSB_TRY(onesweep_launch(c, r, shift, next_shift, nullptr, r.os_hist + lsb::kOnesweepSubs * lsb::kBuckets, x));
   ++*passes;
   r.rg_h[kRgWide] = 0;

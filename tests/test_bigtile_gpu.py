@@ -92,6 +92,22 @@ def test_equal_keys_keep_value_order(lsb_built, monkeypatch):
         assert np.all(out["val"][1:][same] > out["val"][:-1][same])
 
 
+def test_the_size_between(lsb_built, monkeypatch):
+    """LSB_PACKED_TILE=4608 (512 x 9, kept for measurements): the pass that
+    reads the layout counts by 4608, passes 2-5 run 4608 -> 4608, pass 6 the
+    4608 -> 4096 seam; the edge passes have no 4608 instance and keep 4096."""
+    L = lsb_built
+    a = _uniform(N, 11)
+    monkeypatch.setenv("LSB_PACKED_TILE", "4608")
+    with L.World(a.size, ranks=1) as w:
+        w.scatter_global(a)
+        w.my_sort()
+        out = w.gather_global()
+        assert w.last_records() == L.RECORDS_PACKED and w.last_packed_tile() == 4608
+        assert w.last_pass_tiles() == [4096, 4096, 4608, 4608, 4608, 4608, 4608, 4096]
+    assert np.array_equal(out, _stable(a))
+
+
 def test_hot_middle_byte(lsb_built, monkeypatch):
     """Byte 0 uniform (the regional start is taken), half the records share
     byte 3: that pass's hot run is longer than a tile, the passes after it see
