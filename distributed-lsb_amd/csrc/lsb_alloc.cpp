@@ -479,13 +479,24 @@ int alloc_records(lsb_ctx* c, Rank& r) {
 }
 
 // The third record buffer R (receive buffer of the exchanges, the hybrid's
-// third pass buffer), placed like A and B: among up to 3 candidates, the
-// fastest destination (once each, a timed pass B -> candidate that leaves
-// the records in B; B is scratch whenever R is first needed: before a hybrid sort,
-// at an exchange before its placement), each loser freed at once (two
-// buffers live at most).  A may hold records by then and is not touched; the
-// chain counts into histograms of its own, since a sort may hold one in
-// r.os_hist.
+// third pass buffer), placed like A and B: the faster destination of two
+// candidates (once each, a timed pass B -> candidate that leaves the records
+// in B; B is scratch whenever R is first needed: before a hybrid sort, at an
+// exchange before its placement).  Both are live until both are timed (two
+// buffers live at most, as lsb_rank_footprint's probe_bytes says), and the
+// loser is freed then.  It was three candidates, each loser freed at once, so
+// the next was mapped onto the addresses of a range a probe pass had just
+// written and that was then released: the pattern of the VMM fault described
+// above malloc_for, and the hybrid that took such a candidate as R read
+// garbage from it (at 2^28 records 12 passes instead of 4 in 10 of 28 fresh
+// processes, and a wrong sort in two whole-suite runs of three;
+// profiles/r07/alloc_third.txt; 0 of 24 with two candidates).
+// Whether the fault follows the addresses or the pieces is not established;
+// two candidates need neither again while the context lives.  alloc_records
+// keeps its release-then-allocate chain: the LSD sort after it verified in
+// every one of those processes, and what spares it is not established either.
+// A may hold records by then and is not touched; the chain counts into
+// histograms of its own, since a sort may hold one in r.os_hist.
 int alloc_third(lsb_ctx* c, Rank& r) {
   // As many records as A and B: the hybrid permutes the three buffers, and
   // the regional first pass writes into whichever one is B by then.
@@ -493,12 +504,13 @@ int alloc_third(lsb_ctx* c, Rank& r) {
   int K = r.placement_k > 0 ? placement_candidates((double)per * sizeof(Elem), 3) : 1;  // probed A and B only
   if (K <= 2) K = 1;
   if (K == 1 || !r.os_status) return rec_alloc(c, &r.R, per);
+  K = 2;  // probed when three would fit, as before; two are mapped
   uint32_t* hist = nullptr;
   LSB_TRY(dev_alloc(&hist, (size_t)2 * lsb::kOnesweepSubs * lsb::kBuckets));
   Prober pr(r.stream, r.here);
   pr.err = lsb::launch_pcg_fill(r.B, r.here, 0x5eed + 16, 0, lsb::KeyGen(), r.stream);
   Chain ch(r, pr, hist, r.B);
-  Elem* best = nullptr;
+  Elem *best = nullptr, *loser = nullptr;
   double best_ms = 1e300;
   int rc = LSB_OK;
   for (int k = 0; k < K && pr.err == hipSuccess; ++k) {
@@ -509,13 +521,14 @@ int alloc_third(lsb_ctx* c, Rank& r) {
     }
     const double t = ch.attempt(z);  // the records stay in B
     if (t < best_ms) {
-      rec_free(best);
+      loser = best;
       best = z;
       best_ms = t;
     } else {
-      rec_free(z);
+      loser = z;
     }
   }
+  rec_free(loser);
   (void)hipFree(hist);
   if (pr.err != hipSuccess) rc = fail(LSB_ERR_HIP, "alloc_third: placement probe", hipGetErrorString(pr.err));
   if (rc == LSB_OK && !best) rc = fail(LSB_ERR_NOMEM, "alloc_third", "record buffer");

@@ -826,7 +826,7 @@ def test_default_probe_on_large_buffers(lsb_built, monkeypatch):
     """Buffers of at least 4 GiB (2^28 records) take the placement probe by
     default: 4 candidates of VMM pieces, the pair fastest both ways kept
     (DESIGN.md §4), and the sorts that follow, LSD and hybrid (R placed
-    among 3 against B), verify.  LSB_PLACEMENT_CANDIDATES=0 turns it off."""
+    between 2 against B), verify.  LSB_PLACEMENT_CANDIDATES=0 turns it off."""
     monkeypatch.delenv("LSB_PLACEMENT_CANDIDATES", raising=False)
     monkeypatch.delenv("LSB_RECORD_ALLOC", raising=False)
     n = 1 << 28
@@ -841,6 +841,9 @@ def test_default_probe_on_large_buffers(lsb_built, monkeypatch):
         w.generate()
         w.my_sort()
         assert w.verify() == (True, -1)
+        # the four top-byte passes and no more: uniform keys leave no long segment, so the LSD passes
+        # on top of them (12 in all) mean the hybrid met garbage in a buffer (R's probe, alloc_third)
+        assert w.last_sort()[0] == 4
     monkeypatch.setenv("LSB_PLACEMENT_CANDIDATES", "0")
     with lsb_built.World(n, ranks=1) as w:
         assert w.placement()["candidates"] == 0

@@ -6,6 +6,9 @@ The oracle is numpy on the host: the stable argsort of the mapped keys, the
 mapping written out below from the header's table (tests/test_runs_gpu.py's
 model).  Records are loaded with copy_in, their value the global index, so a
 rank's part of the selection, in slot order, is a sorted list of indices.
+What every round reads, and who compacts, is tests/select_model.py's rule of
+the rounds (held against the same argsort in tests/test_select_host.py):
+last_select() must equal it exactly.
 
 The outputs are torch CUDA tensors, so (as tests/test_runs_gpu.py) the tests
 run in one child pytest process over this same file that imports torch before
@@ -26,6 +29,8 @@ import xml.etree.ElementTree as ET
 
 import numpy as np
 import pytest
+
+import select_model as M
 
 IN_CHILD = os.environ.get("LSB_SELECT_CHILD") == "1"
 if IN_CHILD:
@@ -193,6 +198,13 @@ def w_plan(orc, k, P):
     return {"take": [int(x) for x in got["take"]], "bases": [int(x) for x in got["bases"]]}
 
 
+def check_rounds(w, keys, k, what):
+    """The rounds and the records read of the select just run are the model's."""
+    m = M.round_model(keys, w.P, k)
+    assert w.last_select() == (m.rounds, sum(m.read)), (what, k, m.rounds, m.read)
+    return m
+
+
 def check_store(w, orc, k, plan, what, **kw):
     """Every rank's store_select, laid end to end, is the selection in index
     order; the keys are those records' keys."""
@@ -266,6 +278,7 @@ def test_rounds_and_reads(lsb_built):
             orc = Oracle(keys)
             w.copy_in(0, records(keys))
             check_select(w, orc, k, "rounds")
+            check_rounds(w, keys, k, "rounds")
             return w.last_select()
 
         assert run(np.full(n, 77, dtype=np.uint64)) == (1, n)
@@ -292,9 +305,10 @@ def grid_cap():
 
 @torch_first
 def test_more_tiles_than_workgroups(lsb_built):
-    """Every workgroup of k_sel_hist (with the span, with the compaction and
-    plain), of k_sel_count and of k_sel_write takes a second tile, and every
-    thread of k_sel_scan several: n = (grid cap) tiles + one tile + 1."""
+    """The first two workgroups of k_sel_hist (with the span, with the
+    compaction and plain), of k_sel_count and of k_sel_write take a second
+    tile, and every thread of k_sel_scan several: n = (grid cap) tiles + one
+    tile + 1.  (Two tiles for every workgroup: test_dense_two_tiles_each.)"""
     L = lsb_built
     cap, scan_block = grid_cap()
     n = cap * TILE + TILE + 1
@@ -310,6 +324,7 @@ def test_more_tiles_than_workgroups(lsb_built):
         plan = check_select(w, orc, k, "u64")
         rounds, read = w.last_select()
         assert 2 * n < read < 2 * n + n // 16
+        check_rounds(w, keys, k, "u64")
         check_store(w, orc, k, plan, "u64")
         # keys below 2^32: round two reads all of A without a compaction
         keys = rng.integers(0, 1 << 32, n, dtype=np.int64).astype(np.uint64)
@@ -318,6 +333,17 @@ def test_more_tiles_than_workgroups(lsb_built):
         check_select(w, orc, k, "below 2^32")
         rounds, read = w.last_select()
         assert rounds <= 5 and 3 * n < read < 3 * n + n // 16
+        check_rounds(w, keys, k, "below 2^32")
+        # three top-byte values: a third of the records match, and the waves of the two workgroups that
+        # take a second tile flush inside the loop
+        keys = M.top3_keys(n)
+        orc = Oracle(keys)
+        w.copy_in(0, records(keys))
+        for k3 in M.dense_ks(n):
+            plan = check_select(w, orc, k3, "top3")
+            check_rounds(w, keys, k3, "top3")
+            if k3 < k:  # the smallest of the three only: a store's outputs and its check grow with k
+                check_store(w, orc, k3, plan, "top3")
 
 
 # ------------------------------------------------- 4. loopback ranks
@@ -394,6 +420,12 @@ def typed_keys(name, n=N):
         a = (v - 2048) * np.int64(0x0002_0008_0200_0801)
     elif name == "u32":
         a = (v * 0x00100401 % (1 << 32)).astype(np.uint32)
+    elif name == "u64":  # v >= 2048: bit 63 set
+        a = v.astype(np.uint64) * np.uint64(0x0010_0400_8020_0401)
+        assert np.any(a >> np.uint64(63) == 1) and np.any(a >> np.uint64(63) == 0)
+    elif name == "i32":
+        a = ((v - 2048) * 0x00080401).astype(np.int32)
+        assert a.min() < 0 < a.max()
     else:
         a = ((v - 2048) * 0.37).astype(dt) * np.where(v % 3 == 0, dt(1e20), dt(1.0)).astype(dt)
         if name == "f64":
@@ -408,7 +440,8 @@ def typed_keys(name, n=N):
 
 
 @pytest.mark.parametrize("ranks", [1, 3])
-@pytest.mark.parametrize("name,descending", [("i64", False), ("f32", True), ("u32", False), ("f64", False)])
+@pytest.mark.parametrize("name,descending", [("i64", False), ("f32", True), ("u32", False), ("f64", False),
+                                             ("u64", False), ("i32", True)])
 @torch_first
 def test_typed_front_ends(lsb_built, name, descending, ranks):
     import torch
@@ -441,7 +474,7 @@ def test_typed_front_ends(lsb_built, name, descending, ranks):
             values, indices = L.topk(dk, k, largest=largest, sorted=False, ranks=ranks, key_type=key_type)
             assert np.array_equal(host(indices), np.sort(idx)), (largest, k, "unsorted")
             assert np.array_equal(bits_of(host(values)), bits[np.sort(idx)]), (largest, k, "unsorted")
-            if name in ("i64", "f32"):  # NaN-free: torch's values are the same
+            if name in ("i64", "f32", "i32"):  # NaN-free: torch's values are the same
                 tv = torch.topk(torch.from_numpy(keys.copy()), k, largest=largest, sorted=True).values
                 assert np.array_equal(bits_of(host(L.topk(dk, k, largest=largest, ranks=ranks)[0])), bits_of(tv.numpy()))
     assert np.array_equal(bits_of(host(dk)), bits)  # the input is untouched
@@ -561,7 +594,68 @@ def test_state_and_refusals(lsb_built):
         assert np.array_equal(w.copy_out(0), srt)
 
 
-# ------------------------------------------------- 7. real processes
+# ------------------------------------------------- 7. the compaction
+# The inputs of tests/select_model.py, whose conditions (which rounds compact,
+# the fills at the flushes inside the tile loop) tests/test_select_host.py
+# asserts.  A candidate the compaction loses, doubles or replaces moves the
+# pivot of the ks beyond it, or the next round's counts no longer add up.
+def run_compaction(L, keys, P, ks, what):
+    """Every k of ks: the plan against the stable sort, the rounds and reads
+    against the model; the store at the first, middle and last k; A bit for
+    bit afterwards.  No LsbError: a STATE error from the compaction's own
+    checks is a failure like a wrong answer."""
+    rec = records(keys)
+    orc = Oracle(keys)
+    first, mid, last = ks[0], ks[len(ks) // 2], ks[-1]
+    with L.World(keys.size, ranks=P) as w:
+        w.scatter_global(rec)
+        for k in ks:
+            plan = check_select(w, orc, k, what)
+            check_rounds(w, keys, k, what)
+            if k in (first, mid, last):
+                check_store(w, orc, k, plan, what)
+            if k == mid:
+                check_store(w, orc, k, plan, (what, "element-aligned, 4-byte"), shift=1, val_bytes=4)
+        assert np.array_equal(w.gather_global(), rec), what
+
+
+@pytest.mark.parametrize("layout", ["sorted", "shuffled", "one_over"])
+@torch_first
+def test_halving_chain(lsb_built, layout):
+    """Eight rounds, each bucket half of its source: rounds two to eight
+    compact at 2 cand == held, out of A and then out of B into B, until B
+    holds n - n / 128 records.  sorted: tiles that match whole, every flush
+    inside the loop of a full stage.  one_over: 2 cand == held + 2 in the first
+    record's bucket, where round two must filter A again."""
+    run_compaction(lsb_built, M.chain_keys(layout), 1, M.chain_ks(), layout)
+
+
+@torch_first
+def test_three_quarter_blocks(lsb_built):
+    """Three tiles that match at 3/4 in a rank that matches under 1/2: flushes
+    inside the loop with a stage filled to 449..511."""
+    keys = M.blocks_keys()
+    run_compaction(lsb_built, keys, 1, M.bucket_ks(keys, M.BLOCKS_TOP), "blocks")
+
+
+@torch_first
+def test_dense_two_tiles_each(lsb_built):
+    """A third of the records match and every workgroup takes two tiles: nearly
+    every wave flushes inside the loop, across the tile boundary, with a
+    partial stage, and reserves twice."""
+    n = M.dense_n()
+    run_compaction(lsb_built, M.top3_keys(n), 1, M.dense_ks(n), "top3")
+
+
+@torch_first
+def test_mixed_ranks(lsb_built):
+    """Ranks that decide differently in one round: one filters A, one
+    compacts, one has no candidate and launches nothing."""
+    keys = M.mixed_keys()
+    run_compaction(lsb_built, keys, M.MIXED_P, M.mixed_ks(keys)[0], "mixed")
+
+
+# ------------------------------------------------- 8. real processes
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -601,6 +695,7 @@ def _rank_process(rank, world, transport, port, n, k, result_dir, q_uid, q_out):
         w.copy_in(rank, mine)
         w.barrier()
         plan = w.select(k)
+        last = w.last_select()
         m = plan["take"][rank]
         cols = {c: torch.full((m + 2,), SENT, dtype=torch.int64, device="cuda") for c in ("keys", "values")}
         got = w.store_select(rank, **{c: t[1:1 + m] for c, t in cols.items()}, key_type=0)
@@ -612,20 +707,28 @@ def _rank_process(rank, world, transport, port, n, k, result_dir, q_uid, q_out):
         w.close()
         if transport == "gloo":
             dist.destroy_process_group()
-        q_out.put((rank, "ok" if ok else "sentinels, count or A", plan))
+        q_out.put((rank, "ok" if ok else "sentinels, count or A", plan, last))
     except Exception as e:  # report, never hang the parent
-        q_out.put((rank, repr(e), None))
+        q_out.put((rank, repr(e), None, None))
 
 
-def run_processes(tmp_path, world, transport):
+def process_case(world):
+    """-> (mapped keys, k): the pivot group lies across the ranks' boundaries."""
     per = 4099
     n = world * per - 1
     rng = np.random.default_rng(70 + world)
     keys = rng.integers(0, 1 << 62, n, dtype=np.int64).astype(np.uint64)
     keys[per - 6:(2 * per + 11 if world >= 3 else per + 9)] = np.uint64(1 << 61)  # the pivot group across the boundaries
+    lo = int(np.searchsorted(np.sort(keys), np.uint64(1 << 61), "left"))
+    return keys, lo + (per // 2 + 20 if world >= 3 else 8)  # inside the group: the cut falls inside rank 1
+
+
+def run_processes(tmp_path, world, transport, keys, k):
+    """One process per rank selects k of these keys and stores its part ->
+    (the plan, the model of its rounds); every rank's last_select() is the
+    model's."""
+    n = keys.size
     orc = Oracle(keys)
-    lo = int(np.searchsorted(orc.sorted, np.uint64(1 << 61), "left"))
-    k = lo + (per // 2 + 20 if world >= 3 else 8)  # inside the group: the cut falls inside rank 1
     np.save(tmp_path / "input.npy", records(keys))
     ctx = multiprocessing.get_context("spawn")
     q_uid, q_out = ctx.Queue(), ctx.Queue()
@@ -656,13 +759,29 @@ def run_processes(tmp_path, world, transport):
     want = orc.selection(k)
     assert np.array_equal(np.concatenate([p["values"] for p in parts]).astype(np.uint64), want.astype(np.uint64))
     assert np.array_equal(bits_of(np.concatenate([p["keys"] for p in parts])), keys[want])
-    return plan
+    # a rank reads its own records only, in the rounds every rank counts alike
+    m = M.round_model(keys, world, k)
+    lasts = [res[r][3] for r in range(world)]
+    assert lasts == [(m.rounds, m.read[r]) for r in range(world)], (lasts, m.rounds, m.read)
+    return plan, m
 
 
 if not IN_CHILD:
     def test_three_gloo_ranks(lsb_built, tmp_path):
-        plan = run_processes(tmp_path, 3, "gloo")
+        plan, _ = run_processes(tmp_path, 3, "gloo", *process_case(3))
         assert 0 < plan["take"][1] < 4099  # the cut falls inside rank 1, which lies inside the pivot group
 
     def test_two_rccl_ranks(lsb_built, tmp_path):
-        run_processes(tmp_path, 2, "rccl")
+        run_processes(tmp_path, 2, "rccl", *process_case(2))
+
+    def test_three_gloo_ranks_decide_differently(lsb_built, tmp_path):
+        """The mixed ranks, one per process: in round two rank 0 filters A,
+        rank 1 compacts and rank 2 launches nothing and gives zeros to the
+        gather; later rounds have ranks 0 and 1 compact together."""
+        keys = M.mixed_keys()
+        ks, _ = M.mixed_ks(keys)
+        k = ks[len(ks) // 2]
+        plan, m = run_processes(tmp_path, 3, "gloo", keys, k)
+        assert m.trace[1].packed == (False, True, False) and m.trace[1].cand[2] == 0
+        assert any(r.packed[0] and r.packed[1] for r in m.trace[2:])
+        assert m.read[2] == M.MIXED_PER - 1 and plan["take"][2] == 0 and plan["take"][0] > 0 and plan["take"][1] > 0
