@@ -183,6 +183,9 @@ void free_rank(Rank& r, const lsb_ctx* c) {
   (void)hipFree(r.sel_cnt);
   (void)hipFree(r.sel_tbase);
   (void)hipFree(r.search_fence);
+  (void)hipFree(r.join_lower);
+  (void)hipFree(r.join_off);
+  (void)hipFree(r.join_tile);
   (void)hipFree(r.os_status);
   (void)hipFree(r.os_status2);
   (void)hipFree(r.rg_buf);

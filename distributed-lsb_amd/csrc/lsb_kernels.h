@@ -643,4 +643,34 @@ hipError_t launch_search_fence(const Elem* A, int64_t here, uint64_t* fence, hip
 hipError_t launch_search(const Elem* A, int64_t here, const uint64_t* fence, const void* queries, int64_t m,
                          int key_type, int flags, int mode, int64_t* out, hipStream_t s);
 
+// The matches themselves (lsb_search.hip; lsb_lookup, lsb_join_count,
+// lsb_store_join, include/lsb.h).  A, here, fence and the
+// typed queries as for launch_search; the same bounds hold for every probe.
+// Query i with a record of its encoded key e_i: vals[i] = the value of the
+// first such record (val_bytes 8) or its low word (4), found[i] = 1; a query
+// without one touches neither.  vals null exactly when val_bytes is 0; vals or
+// found is given.
+hipError_t launch_lookup(const Elem* A, int64_t here, const uint64_t* fence, const void* queries, int64_t m,
+                         int key_type, int flags, void* vals, int val_bytes, uint8_t* found, hipStream_t s);
+// A rank's join plan: lower[i] = the records below e_i, off[i] = the matches
+// of the queries in front of i (their counts c_i first, then scanned in
+// place), counts[i] = c_i when given, tile[join_qtiles(m)] = the sum of all
+// c_i (tile[t] = the sum over the tiles of kJoinQTile queries before t).
+// m int64 each for lower and off, join_qtiles(m) + 1 for tile.  Three kernels
+// and no wait between workgroups.  lower[i] + c_i <= here whatever A holds.
+constexpr int kJoinQTile = 4096;
+__host__ __device__ inline int64_t join_qtiles(int64_t m) { return (m + kJoinQTile - 1) / kJoinQTile; }
+hipError_t launch_join_count(const Elem* A, int64_t here, const uint64_t* fence, const void* queries, int64_t m,
+                             int key_type, int flags, int64_t* lower, int64_t* off, int64_t* counts, int64_t* tile,
+                             hipStream_t s);
+// Output slot o of [0, total), total > 0 the plan's sum: i = the query with
+// off[i] <= o < off[i + 1] (off[m] = total), p = lower[i] + o - off[i];
+// left[o] = query_base + i, right[o] = A[p].val (val_bytes 8) or its low word
+// (4), pos[o] = gbase + p.  Any output may be null (right exactly when
+// val_bytes is 0), not all.  With lower and off as launch_join_count left
+// them, no index leaves [0, m), [0, here) or [0, total).
+hipError_t launch_join_expand(const Elem* A, int64_t here, const int64_t* lower, const int64_t* off, int64_t m,
+                              int64_t total, int64_t query_base, int64_t gbase, int64_t* left, void* right,
+                              int val_bytes, int64_t* pos, hipStream_t s);
+
 }  // namespace lsb

@@ -16,7 +16,10 @@
 //   lsb_select.cpp    the k-th key and the first k + 1 records without a sort
 //                     (lsb_plan_select, lsb_select, lsb_store_select)
 //   lsb_search.cpp    a column of queries against a rank's sorted records
-//                     (lsb_search)
+//                     (lsb_search) and the fence table the searches share
+//   lsb_join.cpp      the matches themselves: the first match's value per
+//                     query and the matched pairs (lsb_lookup, lsb_join_count,
+//                     lsb_store_join)
 //   lsb_abi.cpp       the extern "C" entry points and the host planners
 //   lsb_xgeom.h       host-only exchange geometry (checked plan, waves); no
 //                     device header, so host tools can include it alone
@@ -174,6 +177,13 @@ struct Rank {
   int64_t* sel_tbase = nullptr;         // [run_tiles(here)][2] those of the tiles before (k_sel_scan)
   // The search (lsb_search.cpp), allocated on first use.
   uint64_t* search_fence = nullptr;     // [run_tiles(here)] the key of every tile's first record (k_search_fence)
+  // The join plan (lsb_join.cpp), allocated at the first lsb_join_count and
+  // regrown when a later one has more queries.
+  int64_t* join_lower = nullptr;        // [join_cap] the records below every query
+  int64_t* join_off = nullptr;          // [join_cap] the matches of the queries in front of every query
+  int64_t* join_tile = nullptr;         // [join_qtiles(join_cap) + 1] tile bases of the scan, then the total
+  int64_t join_cap = 0;                 // queries the three hold
+  int64_t join_m = 0, join_total = 0;   // the plan: its queries and its pairs
   std::vector<int64_t> send_counts, send_displs, recv_counts, recv_displs;
 };
 
@@ -253,6 +263,9 @@ struct lsb_ctx {
   // until an entry point that can change A (search_invalidate).  lsb_select
   // leaves A bit for bit and writes B only, so it keeps the fences.
   uint64_t search_valid = 0;
+  // Bit r: rank r's join plan (join_lower, join_off, join_m, join_total) is
+  // that of its A (lsb_join_count), for as long as its fence table would be.
+  uint64_t join_valid = 0;
   lsb::KeyGen keygen;
   std::vector<lsb_rt::PendingEvent> pending;
   std::vector<std::pair<int, hipEvent_t>> event_pool;  // (device, event) of finished timings
@@ -404,8 +417,12 @@ int check_ctx(const lsb_ctx* c);
 inline void runs_invalidate(lsb_ctx* c) { c->runs_valid = c->reduce_valid = c->scan_valid = false; }
 // A is about to change: lsb_store_select needs a new lsb_select.
 inline void select_invalidate(lsb_ctx* c) { c->select_valid = false; }
-// A is about to change: lsb_search builds a rank's fence table again.
-inline void search_invalidate(lsb_ctx* c) { c->search_valid = 0; }
+// A is about to change: the searches build a rank's fence table again, and
+// lsb_store_join needs a new lsb_join_count.
+inline void search_invalidate(lsb_ctx* c) { c->search_valid = c->join_valid = 0; }
+// r's fence table, allocated and built when search_valid says so
+// (lsb_search.cpp); r.here > 0, r's device current, r's stream idle or ahead.
+int ensure_search_fence(lsb_ctx* c, Rank& r);
 // A caller's column of cnt elements of `elem` bytes at p, before a kernel may
 // touch it (lsb_context.cpp): LSB_ERR_INVALID unless it is aligned to its element,
 // device (or managed) memory of the rank's device and inside its allocation.

@@ -1,10 +1,24 @@
 // A column of queries against a rank's sorted records (include/lsb.h,
 // DESIGN.md §7.7): the argument checks, the rank's fence table (built at the
-// first search after a change of A) and the one launch of lsb_search.
+// first search after a change of A, for lsb_lookup and lsb_join_count too) and
+// the one launch of lsb_search.
 #include "lsb_keyform.h"
 #include "lsb_rt.h"
 
 using namespace lsb_rt;
+
+namespace lsb_rt {
+
+int ensure_search_fence(lsb_ctx* c, Rank& r) {
+  if (!r.search_fence) LSB_TRY(dev_alloc(&r.search_fence, (size_t)lsb::run_tiles(r.here)));
+  if (!((c->search_valid >> r.rank) & 1)) {
+    HIP_TRY(lsb::launch_search_fence(r.A, r.here, r.search_fence, r.stream));
+    c->search_valid |= 1ull << r.rank;
+  }
+  return LSB_OK;
+}
+
+}  // namespace lsb_rt
 
 extern "C" {
 
@@ -33,11 +47,7 @@ int lsb_search(lsb_ctx_t* c, int rank, int64_t m, const void* queries_dev, int k
   if (r->here == 0) {  // no record counts: zeros, or nothing to add
     if (!add) HIP_TRY(hipMemsetAsync(out_dev, 0, (size_t)m * sizeof(int64_t), r->stream));
   } else {
-    if (!r->search_fence) LSB_TRY(dev_alloc(&r->search_fence, (size_t)lsb::run_tiles(r->here)));
-    if (!((c->search_valid >> rank) & 1)) {
-      HIP_TRY(lsb::launch_search_fence(r->A, r->here, r->search_fence, r->stream));
-      c->search_valid |= 1ull << rank;
-    }
+    LSB_TRY(ensure_search_fence(c, *r));
     HIP_TRY(lsb::launch_search(r->A, r->here, r->search_fence, queries_dev, m, key_type, flags, mode, out_dev,
                                r->stream));
   }

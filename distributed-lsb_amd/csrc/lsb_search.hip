@@ -14,6 +14,9 @@
 // bounded by construction: a probe index comes from [lo, hi) of a range that
 // starts inside the rank's records and only shrinks, so unsorted records give
 // unspecified counts, never a read outside A.
+// The kernels that hand the matches back (lsb_lookup, lsb_join_count,
+// lsb_store_join) stand behind k_search and search with the
+// same bound<> and run_from.
 #include "lsb_kernels.h"
 #include "lsb_keyform.h"
 
@@ -193,7 +196,304 @@ void search_type(const Elem* A, int64_t here, const uint64_t* fence, const void*
   }
 }
 
+// ---- lookup and join (lsb_lookup, lsb_join_count, lsb_store_join) ----
+//   k_lookup        k_search's loop with the lower bound, one key compare, a
+//                   guarded store of the first match's value and the found byte
+//   k_join_count    per query its lower bound and its run (k_search's COUNT,
+//                   both numbers kept), and the runs' sum per tile of queries
+//   k_join_scan     one workgroup: tile sums -> exclusive tile bases, in sweeps
+//   k_join_offsets  counts -> exclusive offsets, in place, a tile per workgroup
+//   k_join_expand   a tile of outputs per workgroup: the queries that meet it
+//                   by two wave-wide searches of the offsets, their offsets in
+//                   LDS, then every output finds its query there
+// Reduce-then-scan, as the tile counts of lsb_runs.hip and lsb_select.hip: no
+// kernel waits for another workgroup.
+constexpr int kJoinQItems = kJoinQTile / kSearchBlock;
+constexpr int kJoinScanSweep = 256;  // tile sums k_join_scan takes per sweep, one per thread
+constexpr int kJoinBlock = 256;      // 4 waves
+constexpr int kJoinTile = 2048;      // T: outputs per workgroup of k_join_expand
+constexpr int kJoinSpan = 4096;      // S: offsets a workgroup stages in LDS (32 KiB); a longer span is searched in global memory
+constexpr int kJoinItems = kJoinTile / kJoinBlock;
+static_assert(kJoinQTile % kSearchBlock == 0 && kJoinTile % kJoinBlock == 0 && kSearchBlock == 256, "join tile shapes");
+
+// top[j] = fence[j * step], as k_search stages it; the barrier included.
+__device__ __forceinline__ int64_t stage_top(const uint64_t* __restrict__ fence, int64_t tiles, uint64_t* top) {
+  const int64_t step = (tiles + kSearchTop - 1) / kSearchTop;
+  for (int64_t j = threadIdx.x; j * step < tiles; j += kSearchBlock) top[j] = fence[j * step];  // j < kSearchTop
+  __syncthreads();
+  return step;
+}
+
+// Grid-stride as k_search.  A query with a match writes the elements it owns;
+// one without touches nothing.
+template <typename KeyT>
+__global__ __launch_bounds__(kSearchBlock) void k_lookup(const Elem* __restrict__ A, int64_t here,
+                                                         const uint64_t* __restrict__ fence, int64_t tiles,
+                                                         const KeyT* __restrict__ queries, int64_t m, int key_type,
+                                                         int flags, void* __restrict__ vals, int val_bytes,
+                                                         uint8_t* __restrict__ found) {
+  __shared__ uint64_t top[kSearchTop];
+  const uint64_t* __restrict__ keys = reinterpret_cast<const uint64_t*>(A);
+  const KeyForm form = key_form(key_type, flags);
+  const uint64_t first = fence[0], last = keys[2 * (here - 1)];
+  const int64_t step = stage_top(fence, tiles, top);
+  const int64_t stride = (int64_t)gridDim.x * kSearchBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kSearchBlock + threadIdx.x; i < m; i += stride) {
+    const uint64_t e = encode((uint64_t)__builtin_nontemporal_load(queries + i), form);
+    const int64_t lo = bound<false>(keys, here, fence, tiles, top, step, first, last, e);
+    LSB_SEARCH_ASSERT(lo >= 0 && lo <= here);
+    if (lo >= here || keys[2 * lo] != e) continue;
+    if (val_bytes == 8) static_cast<uint64_t*>(vals)[i] = keys[2 * lo + 1];
+    else if (val_bytes == 4) static_cast<uint32_t*>(vals)[i] = (uint32_t)keys[2 * lo + 1];
+    if (found) found[i] = 1;
+  }
+}
+
+// A tile of kJoinQTile queries per workgroup and sweep, lane-striped: lower[i]
+// and cnt[i] of every query, counts[i] = cnt[i] too when given, and
+// tile_sum[t] = the tile's sum of cnt.  lower[i] + cnt[i] <= here whatever A
+// holds (bound<> and run_from).
+template <typename KeyT>
+__global__ __launch_bounds__(kSearchBlock) void k_join_count(const Elem* __restrict__ A, int64_t here,
+                                                             const uint64_t* __restrict__ fence, int64_t tiles,
+                                                             const KeyT* __restrict__ queries, int64_t m, int key_type,
+                                                             int flags, int64_t* __restrict__ lower,
+                                                             int64_t* __restrict__ cnt, int64_t* __restrict__ counts,
+                                                             int64_t* __restrict__ tile_sum) {
+  __shared__ uint64_t top[kSearchTop];
+  __shared__ int64_t s_wave[kSearchBlock / 64];
+  const uint64_t* __restrict__ keys = reinterpret_cast<const uint64_t*>(A);
+  const KeyForm form = key_form(key_type, flags);
+  const uint64_t first = fence[0], last = keys[2 * (here - 1)];
+  const int64_t step = stage_top(fence, tiles, top);
+  const int64_t qtiles = join_qtiles(m);
+  for (int64_t t = blockIdx.x; t < qtiles; t += gridDim.x) {
+    int64_t sum = 0;
+    for (int j = 0; j < kJoinQItems; ++j) {
+      const int64_t i = t * kJoinQTile + j * kSearchBlock + threadIdx.x;
+      if (i >= m) break;
+      const uint64_t e = encode((uint64_t)__builtin_nontemporal_load(queries + i), form);
+      const int64_t lo = bound<false>(keys, here, fence, tiles, top, step, first, last, e);
+      const int64_t c = run_from(keys, here, e, lo);
+      LSB_SEARCH_ASSERT(lo >= 0 && c >= 0 && lo + c <= here);
+      lower[i] = lo;
+      cnt[i] = c;
+      if (counts) counts[i] = c;
+      sum += c;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off, 64);
+    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) tile_sum[t] = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+    __syncthreads();
+  }
+}
+
+// One workgroup: tile[t] = the sums of the tiles before t, in place, and
+// tile[qtiles] = the sum of all.  kJoinScanSweep tiles per sweep, one per
+// thread; the sweeps before are carried in a register that every thread keeps.
+__global__ __launch_bounds__(kJoinScanSweep) void k_join_scan(int64_t qtiles, int64_t* __restrict__ tile) {
+  __shared__ int64_t s[kJoinScanSweep];
+  const int tid = (int)threadIdx.x;
+  int64_t carry = 0;
+  for (int64_t t0 = 0; t0 < qtiles; t0 += kJoinScanSweep) {
+    const int64_t t = t0 + tid;
+    const int64_t mine = t < qtiles ? tile[t] : 0;
+    s[tid] = mine;
+    __syncthreads();
+    for (int off = 1; off < kJoinScanSweep; off <<= 1) {
+      const int64_t a = tid >= off ? s[tid - off] : 0;
+      __syncthreads();
+      s[tid] += a;
+      __syncthreads();
+    }
+    if (t < qtiles) tile[t] = carry + s[tid] - mine;
+    carry += s[kJoinScanSweep - 1];
+    __syncthreads();  // s is written again
+  }
+  if (tid == 0) tile[qtiles] = carry;
+}
+
+// A tile of kJoinQTile counts per workgroup and sweep, kJoinQItems adjacent
+// ones per thread: cnt[i] -> tile_base[t] + the counts of the tile in front
+// of i, in place.
+__global__ __launch_bounds__(kSearchBlock) void k_join_offsets(int64_t m, const int64_t* __restrict__ tile_base,
+                                                               int64_t* __restrict__ cnt) {
+  __shared__ int64_t s_wave[kSearchBlock / 64];
+  const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
+  const int64_t qtiles = join_qtiles(m);
+  for (int64_t t = blockIdx.x; t < qtiles; t += gridDim.x) {
+    const int64_t i0 = t * kJoinQTile + (int64_t)threadIdx.x * kJoinQItems;
+    int64_t c[kJoinQItems];
+    int64_t sum = 0;
+#pragma unroll
+    for (int j = 0; j < kJoinQItems; ++j) {
+      c[j] = i0 + j < m ? cnt[i0 + j] : 0;
+      sum += c[j];
+    }
+    int64_t incl = sum;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const int64_t o = __shfl_up(incl, off, 64);
+      if (lane >= off) incl += o;
+    }
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    int64_t base = tile_base[t] + incl - sum;
+    for (int w = 0; w < wave; ++w) base += s_wave[w];
+#pragma unroll
+    for (int j = 0; j < kJoinQItems; ++j) {
+      if (i0 + j < m) cnt[i0 + j] = base;
+      base += c[j];
+    }
+    __syncthreads();
+  }
+}
+
+// The entries of off[0, m) that are not above x (off ascending, off[0] <= x
+// in every call: >= 1), by one whole wave: its lanes probe 64 places spread
+// over the range, the ballot tells between which two the answer lies.  Every
+// probe index lies in [0, m); the result is the same in every lane.
+__device__ __forceinline__ int64_t wave_not_above(const int64_t* __restrict__ off, int64_t m, int64_t x) {
+  const int lane = (int)(threadIdx.x & 63);
+  int64_t lo = 0, hi = m;
+  while (lo < hi) {
+    const int64_t step = (hi - lo + 63) >> 6;
+    const int64_t idx = lo + lane * step;
+    LSB_SEARCH_ASSERT(idx >= 0 && (idx >= hi || idx < m));
+    const bool in = idx < hi && off[idx] <= x;
+    const int k = __popcll(__ballot(in));  // the probes that are not above x: a prefix of the lanes
+    if (k == 0) {
+      hi = lo;
+    } else {
+      const int64_t end = lo + k * step;
+      lo += (k - 1) * step + 1;
+      hi = end < hi ? end : hi;
+    }
+  }
+  return lo;
+}
+
+// base[j] = the last index k of a[0, len) with a[k] <= x[j], for N values at
+// once; a ascending, len >= 1 and a[0] <= x[j].  The trip count depends on len
+// alone, so the N searches advance together and their loads overlap.
+template <int N>
+__device__ __forceinline__ void last_not_above(const int64_t* a, int64_t len, const int64_t (&x)[N], int64_t (&base)[N]) {
+  const int64_t n = len;
+  (void)n;
+#pragma unroll
+  for (int j = 0; j < N; ++j) base[j] = 0;
+  while (len > 1) {
+    const int64_t half = len >> 1;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      LSB_SEARCH_ASSERT(base[j] >= 0 && base[j] + half < n);
+      if (a[base[j] + half] <= x[j]) base[j] += half;
+    }
+    len -= half;
+  }
+}
+
+// Workgroup b writes the outputs [b * kJoinTile, (b + 1) * kJoinTile) of
+// [0, total): output o of query i = the last one with off[i] <= o (the
+// queries without a match share their successor's offset and are never the
+// last) is record p = lower[i] + o - off[i].  Adjacent lanes take adjacent
+// outputs, and inside one query's range adjacent records.
+__global__ __launch_bounds__(kJoinBlock) void k_join_expand(const Elem* __restrict__ A, int64_t here,
+                                                            const int64_t* __restrict__ lower,
+                                                            const int64_t* __restrict__ off, int64_t m, int64_t total,
+                                                            int64_t query_base, int64_t gbase,
+                                                            int64_t* __restrict__ left, void* __restrict__ right,
+                                                            int val_bytes, int64_t* __restrict__ pos) {
+  __shared__ int64_t s_off[kJoinSpan];
+  __shared__ int64_t s_q[2];
+  const int tid = (int)threadIdx.x;
+  const int64_t o0 = (int64_t)blockIdx.x * kJoinTile;
+  const int64_t o1 = o0 + kJoinTile < total ? o0 + kJoinTile : total;  // o0 < total: the grid is ceil(total / kJoinTile)
+  // The first and the last query whose outputs meet the tile, one wave each.
+  if (tid < 128) {
+    const int64_t q = wave_not_above(off, m, tid < 64 ? o0 : o1 - 1) - 1;
+    if ((tid & 63) == 0) s_q[tid >> 6] = q;
+  }
+  __syncthreads();
+  const int64_t q0 = s_q[0], span = s_q[1] - q0 + 1;
+  LSB_SEARCH_ASSERT(q0 >= 0 && span >= 1 && q0 + span <= m);
+  const bool staged = span <= kJoinSpan;  // the same in every thread
+  if (staged) {
+    for (int64_t k = tid; k < span; k += kJoinBlock) s_off[k] = off[q0 + k];
+    __syncthreads();
+  }
+  int64_t o[kJoinItems], k[kJoinItems];
+#pragma unroll
+  for (int j = 0; j < kJoinItems; ++j) {
+    const int64_t mine = o0 + j * kJoinBlock + tid;
+    o[j] = mine < o1 ? mine : o1 - 1;  // past the end: searched like the last output, not stored
+  }
+  if (staged) last_not_above(s_off, span, o, k);
+  else last_not_above(off + q0, span, o, k);
+#pragma unroll
+  for (int j = 0; j < kJoinItems; ++j) {
+    if (o0 + j * kJoinBlock + tid >= o1) continue;
+    const int64_t i = q0 + k[j];
+    const int64_t p = lower[i] + (o[j] - (staged ? s_off[k[j]] : off[i]));
+    LSB_SEARCH_ASSERT(i >= 0 && i < m && p >= 0 && p < here && o[j] >= 0 && o[j] < total);
+    if (left) left[o[j]] = query_base + i;
+    if (val_bytes == 8) static_cast<uint64_t*>(right)[o[j]] = A[p].val;
+    else if (val_bytes == 4) static_cast<uint32_t*>(right)[o[j]] = (uint32_t)A[p].val;
+    if (pos) pos[o[j]] = gbase + p;
+  }
+}
+
 }  // namespace
+
+hipError_t launch_lookup(const Elem* A, int64_t here, const uint64_t* fence, const void* queries, int64_t m,
+                         int key_type, int flags, void* vals, int val_bytes, uint8_t* found, hipStream_t s) {
+  if (!A || here <= 0 || !fence || !queries || m <= 0 || !key_form_valid(key_type, flags) ||
+      (val_bytes != 0 && val_bytes != 4 && val_bytes != 8) || (val_bytes == 0) != (vals == nullptr) ||
+      (!vals && !found))
+    return hipErrorInvalidValue;
+  const int64_t tiles = run_tiles(here);
+  const dim3 grid(search_grid(m)), block(kSearchBlock);
+  if (key_bytes(key_type) == 4)
+    hipLaunchKernelGGL(k_lookup<uint32_t>, grid, block, 0, s, A, here, fence, tiles,
+                       static_cast<const uint32_t*>(queries), m, key_type, flags, vals, val_bytes, found);
+  else
+    hipLaunchKernelGGL(k_lookup<uint64_t>, grid, block, 0, s, A, here, fence, tiles,
+                       static_cast<const uint64_t*>(queries), m, key_type, flags, vals, val_bytes, found);
+  return hipGetLastError();
+}
+
+hipError_t launch_join_count(const Elem* A, int64_t here, const uint64_t* fence, const void* queries, int64_t m,
+                             int key_type, int flags, int64_t* lower, int64_t* off, int64_t* counts, int64_t* tile,
+                             hipStream_t s) {
+  if (!A || here <= 0 || !fence || !queries || m <= 0 || !key_form_valid(key_type, flags) || !lower || !off || !tile)
+    return hipErrorInvalidValue;
+  const int64_t tiles = run_tiles(here), qtiles = join_qtiles(m);
+  const dim3 grid((unsigned)(qtiles > kSearchGridCap ? kSearchGridCap : qtiles)), block(kSearchBlock);
+  if (key_bytes(key_type) == 4)
+    hipLaunchKernelGGL(k_join_count<uint32_t>, grid, block, 0, s, A, here, fence, tiles,
+                       static_cast<const uint32_t*>(queries), m, key_type, flags, lower, off, counts, tile);
+  else
+    hipLaunchKernelGGL(k_join_count<uint64_t>, grid, block, 0, s, A, here, fence, tiles,
+                       static_cast<const uint64_t*>(queries), m, key_type, flags, lower, off, counts, tile);
+  hipLaunchKernelGGL(k_join_scan, dim3(1), dim3(kJoinScanSweep), 0, s, qtiles, tile);
+  hipLaunchKernelGGL(k_join_offsets, grid, block, 0, s, m, tile, off);
+  return hipGetLastError();
+}
+
+hipError_t launch_join_expand(const Elem* A, int64_t here, const int64_t* lower, const int64_t* off, int64_t m,
+                              int64_t total, int64_t query_base, int64_t gbase, int64_t* left, void* right,
+                              int val_bytes, int64_t* pos, hipStream_t s) {
+  const int64_t blocks = total > 0 ? (total + kJoinTile - 1) / kJoinTile : 0;
+  if (!A || here <= 0 || !lower || !off || m <= 0 || total <= 0 || total > m * here || blocks > 0x7fffffff ||
+      (val_bytes != 0 && val_bytes != 4 && val_bytes != 8) || (val_bytes == 0) != (right == nullptr) ||
+      (!left && !right && !pos))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_join_expand, dim3((unsigned)blocks), dim3(kJoinBlock), 0, s, A, here, lower, off, m, total,
+                     query_base, gbase, left, right, val_bytes, pos);
+  return hipGetLastError();
+}
 
 hipError_t launch_search_fence(const Elem* A, int64_t here, uint64_t* fence, hipStream_t s) {
   if (!A || here <= 0 || !fence) return hipErrorInvalidValue;

@@ -33,7 +33,10 @@ in the group, the group's start) from ``group_scan(keys, values)``,
 records need no sort: ``kth(keys, k)`` and ``topk(keys, k)``, or ``World.select`` /
 ``World.store_select``.  A second column is searched against the sorted one
 (where each key would go, whether and how often it occurs) with
-``searchsorted(keys, queries)``, ``count_of`` and ``isin``, or ``World.search``.
+``searchsorted(keys, queries)``, ``count_of`` and ``isin``, or ``World.search``;
+the matches themselves come from ``lookup(keys, values, queries)`` (the value
+stored with each query's key) and ``join(left_keys, right_keys)`` (all pairs of
+equal keys), or ``World.lookup`` / ``World.join_count`` / ``World.store_join``.
 torch is imported only inside those functions.  A process that uses them imports torch before the first call into
 this module: the library then binds to the HIP runtime torch brought, and both
 see the same device memory.
@@ -224,6 +227,9 @@ def _lib() -> ctypes.CDLL:
             "lsb_store_select": (i32, [vp, i32, i64, vp, i32, i32, vp, i32, P64]),
             "lsb_get_last_select": (i32, [vp, ctypes.POINTER(ctypes.c_int), P64]),
             "lsb_search": (i32, [vp, i32, i64, vp, i32, i32, i32, vp]),
+            "lsb_lookup": (i32, [vp, i32, i64, vp, i32, i32, vp, i32, vp]),
+            "lsb_join_count": (i32, [vp, i32, i64, vp, i32, i32, vp, P64]),
+            "lsb_store_join": (i32, [vp, i32, i64, i64, vp, vp, i32, vp, P64]),
             "lsb_sort": (i32, [vp]),
             "lsb_pass": (i32, [vp, i32]),
             "lsb_sync": (i32, [vp]),
@@ -253,7 +259,8 @@ def _lib() -> ctypes.CDLL:
         for name, (res, args) in sig.items():
             # An older build given through LSB_LIBRARY (A/B timing against the
             # parent commit) lacks the newest entry points; calling them there raises.
-            if name in ("lsb_get_last_packed_tile", "lsb_get_last_pass_tiles", "lsb_search") and not hasattr(L, name):
+            if name in ("lsb_get_last_packed_tile", "lsb_get_last_pass_tiles", "lsb_search", "lsb_lookup",
+                        "lsb_join_count", "lsb_store_join") and not hasattr(L, name):
                 continue
             fn = getattr(L, name)
             fn.restype = res
@@ -806,6 +813,108 @@ def isin(queries, keys, descending: bool = False, ranks: int = 1, radix_bits: in
     return _search(keys, queries, "count", descending, ranks, radix_bits, key_type, assume_sorted) > 0
 
 
+def lookup(keys, values, queries, default=0, descending: bool = False, ranks: int = 1, radix_bits: int = 8,
+           key_type: Optional[int] = None, assume_sorted: bool = False):
+    """The value stored with every query's key: (out, found).  out has the
+    values' dtype and the queries' length, prefilled with `default`; where the
+    key occurs, out[i] = the value of its first occurrence (among equal keys
+    the one that comes first in keys; with assume_sorted the first in the given
+    order) and found[i] (bool) is True.  values=None looks up the input index
+    of that first occurrence (int64).  Keys are equal when their bits are;
+    the remaining arguments are searchsorted()'s.  One World(n, ranks) loads
+    keys and values, sorts them unless assume_sorted, and looks the queries up
+    on every non-empty rank, from the last to the first, so that the lowest
+    rank's match stands."""
+    import torch
+    _check_column(keys, "keys")
+    kt = _key_type_of(keys, key_type)
+    _check_column(queries, "queries", keys.device)
+    if _key_type_of(queries, key_type) != kt:
+        raise ValueError(f"queries of {queries.dtype} against keys of {keys.dtype}")
+    if values is not None:
+        _check_column(values, "values", keys.device)
+        if values.numel() != keys.numel():
+            raise ValueError("keys and values differ in length")
+    if ranks < 1:
+        raise ValueError("ranks")
+    n, m = keys.numel(), queries.numel()
+    out = torch.full((m,), default, dtype=torch.int64 if values is None else values.dtype, device=keys.device)
+    found = torch.zeros(m, dtype=torch.uint8, device=keys.device)
+    if n == 0 or m == 0:
+        return out, found.bool()
+    dev = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
+    with World(n, ranks=ranks, devices=[dev] * ranks, radix_bits=radix_bits) as w:
+        blocks = [(r, r * w.per, w.here(r)) for r in range(ranks) if w.here(r)]
+        for r, lo, h in blocks:
+            w.load_columns(r, keys[lo:lo + h], None if values is None else values[lo:lo + h],
+                           descending=descending, key_type=kt)
+        if not assume_sorted:
+            w.my_sort()
+        for r, _, _ in reversed(blocks):
+            w.lookup(r, queries, out, found, descending=descending, key_type=kt)
+    return out, found.bool()
+
+
+_JOIN_HOW = ("inner", "left")
+
+
+def join(left_keys, right_keys, how: str = "inner", descending: bool = False, ranks: int = 1, radix_bits: int = 8,
+         key_type: Optional[int] = None, assume_sorted: bool = False):
+    """All pairs of equal keys of two device columns: (left_index, right_index),
+    both int64, left_keys[left_index[j]] == right_keys[right_index[j]] on the
+    bits, every such pair once.  One World(n, ranks) loads right_keys with
+    their indices and sorts them (unless assume_sorted says they are sorted in
+    that order already), then counts and stores the pairs of every non-empty
+    rank, in rank order.  ranks=1: ordered by left index, then by right index;
+    more ranks: each rank's pairs in that order, rank after rank.
+    how="left" appends (i, -1) for every left key without a match, after the
+    matched pairs and in left order.  No keys on either side: no matched
+    pair.  The remaining arguments are searchsorted()'s, right_keys being the
+    sorted side."""
+    import torch
+    if how not in _JOIN_HOW:
+        raise ValueError(f"how {how!r}: not one of {_JOIN_HOW}")
+    _check_column(right_keys, "right_keys")
+    kt = _key_type_of(right_keys, key_type)
+    _check_column(left_keys, "left_keys", right_keys.device)
+    if _key_type_of(left_keys, key_type) != kt:
+        raise ValueError(f"left keys of {left_keys.dtype} against right keys of {right_keys.dtype}")
+    if ranks < 1:
+        raise ValueError("ranks")
+    n, m = right_keys.numel(), left_keys.numel()
+    device = right_keys.device
+    lefts, rights = [], []
+    matched = torch.zeros(m, dtype=torch.int64, device=device)
+    if n > 0 and m > 0:
+        dev = device.index if device.index is not None else torch.cuda.current_device()
+        with World(n, ranks=ranks, devices=[dev] * ranks, radix_bits=radix_bits) as w:
+            blocks = [(r, r * w.per, w.here(r)) for r in range(ranks) if w.here(r)]
+            for r, lo, h in blocks:
+                w.load_columns(r, right_keys[lo:lo + h], None, descending=descending, key_type=kt)
+            if not assume_sorted:
+                w.my_sort()
+            counts = torch.empty(m, dtype=torch.int64, device=device) if how == "left" else None
+            for r, _, _ in blocks:
+                total = w.join_count(r, left_keys, counts, descending=descending, key_type=kt)
+                if counts is not None:
+                    matched += counts
+                if total == 0:
+                    continue
+                li = torch.empty(total, dtype=torch.int64, device=device)
+                ri = torch.empty(total, dtype=torch.int64, device=device)
+                w.store_join(r, left=li, right=ri)
+                lefts.append(li)
+                rights.append(ri)
+    if how == "left":
+        lone = torch.nonzero(matched == 0).flatten()
+        lefts.append(lone)
+        rights.append(torch.full_like(lone, -1))
+    if not lefts:
+        empty = torch.empty(0, dtype=torch.int64, device=device)
+        return empty, empty.clone()
+    return torch.cat(lefts), torch.cat(rights)
+
+
 def plan_select(n: int, P: int, count: int, below: np.ndarray, equal: np.ndarray) -> dict:
     """lsb_plan_select, the host planner of the select: below[r], equal[r] =
     rank r's records below and equal to the pivot, count = k + 1 wanted
@@ -1246,6 +1355,94 @@ class World:
                                  ORDER_DESCENDING if descending else 0,
                                  _SEARCH_SIDES[side] | (SEARCH_ADD if add else 0), out.data_ptr() if m else None),
                "lsb_search")
+
+    def lookup(self, rank: int, queries, values=None, found=None, descending: bool = False,
+               key_type: Optional[int] = None, val_bytes: Optional[int] = None) -> None:
+        """lsb_lookup: for every query with a record of its key on `rank`
+        (sorted), values[i] = the value of the first such record (a 4-byte
+        dtype gets the low word; val_bytes= overrides the element size) and
+        found[i] = 1 (a uint8 or bool column); a query without one leaves both
+        elements as they are.  queries as for search(); values and found the
+        queries' length, on their device, no byte shared; either may be None,
+        not both.  Local, no collective: called from the last rank to the
+        first, the lowest rank's match stands."""
+        import torch
+        _check_column(queries, "queries")
+        kt = _key_type_of(queries, key_type)
+        if values is None and found is None:
+            raise ValueError("no output column")
+        m = queries.numel()
+        if values is not None:
+            _check_column(values, "values", queries.device)
+            if values.numel() != m:
+                raise ValueError("queries and values differ in length")
+        if found is not None:
+            if not isinstance(found, torch.Tensor) or not found.is_cuda or found.device != queries.device:
+                raise ValueError("found: not a tensor on the queries' GPU")
+            if found.dtype not in (torch.uint8, torch.bool) or found.dim() != 1 or not found.is_contiguous():
+                raise ValueError("found: not a 1-D contiguous uint8 or bool column")
+            if found.numel() != m:
+                raise ValueError("queries and found differ in length")
+        vb = 0 if values is None else (values.element_size() if val_bytes is None else val_bytes)
+        torch.cuda.current_stream(queries.device).synchronize()
+        _check(_lib().lsb_lookup(self._h, rank, m, queries.data_ptr() if m else None, kt,
+                                 ORDER_DESCENDING if descending else 0,
+                                 None if values is None else (values.data_ptr() if m else values.new_empty(1).data_ptr()),
+                                 vb, None if found is None else (found.data_ptr() if m else found.new_empty(1).data_ptr())),
+               "lsb_lookup")
+
+    def join_count(self, rank: int, queries, counts=None, descending: bool = False,
+                   key_type: Optional[int] = None) -> int:
+        """lsb_join_count: `rank`'s join plan for these queries (kept by the
+        library until the records change or the rank counts again) -> the
+        pairs it holds.  counts (optional): int64, the queries' length and
+        device, no byte shared: the matches of every query on this rank."""
+        import torch
+        _check_column(queries, "queries")
+        kt = _key_type_of(queries, key_type)
+        m = queries.numel()
+        if counts is not None:
+            _check_column(counts, "counts", queries.device)
+            if counts.dtype != torch.int64:
+                raise ValueError("counts: not int64")
+            if counts.numel() != m:
+                raise ValueError("queries and counts differ in length")
+        torch.cuda.current_stream(queries.device).synchronize()
+        total = ctypes.c_int64()
+        _check(_lib().lsb_join_count(self._h, rank, m, queries.data_ptr() if m else None, kt,
+                                     ORDER_DESCENDING if descending else 0,
+                                     counts.data_ptr() if counts is not None and m else None, ctypes.byref(total)),
+               "lsb_join_count")
+        return int(total.value)
+
+    def store_join(self, rank: int, left=None, right=None, pos=None, query_base: int = 0,
+                   val_bytes: Optional[int] = None) -> int:
+        """lsb_store_join: the pairs of `rank`'s join plan into device columns
+        (1-D contiguous CUDA torch tensors, any may be None, not all): left =
+        query_base + the query's index and pos = the record's global position
+        (both int64), right = the record's value (any 4- or 8-byte dtype; 4:
+        the low word; val_bytes= overrides the element size).  Ordered by
+        query, then by record.  Every column holds at least the rank's pairs;
+        -> their number."""
+        import torch
+        cols = [(t, what) for t, what in ((left, "left"), (right, "right"), (pos, "pos")) if t is not None]
+        if not cols:
+            raise ValueError("no output column")
+        for t, what in cols:
+            _check_column(t, what, cols[0][0].device)
+            if what != "right" and t.dtype != torch.int64:
+                raise ValueError(f"{what}: not int64")
+        cap = min(t.numel() for t, _ in cols)
+        if cap == 0:  # an empty tensor has no address: stand-ins say which outputs are meant (cap 0: never written)
+            left, right, pos = (None if t is None else t.new_empty(1) for t in (left, right, pos))
+        vb = 0 if right is None else (right.element_size() if val_bytes is None else val_bytes)
+        torch.cuda.current_stream(cols[0][0].device).synchronize()
+        count = ctypes.c_int64()
+        _check(_lib().lsb_store_join(self._h, rank, cap, query_base, None if left is None else left.data_ptr(),
+                                     None if right is None else right.data_ptr(), vb,
+                                     None if pos is None else pos.data_ptr(), ctypes.byref(count)),
+               "lsb_store_join")
+        return int(count.value)
 
     def scatter_global(self, arr: np.ndarray) -> None:
         """Load a global array of n records into the block partition."""

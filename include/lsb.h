@@ -782,6 +782,101 @@ int  lsb_get_last_select(lsb_ctx_t* ctx, int* rounds, int64_t* records_read);
 int  lsb_search(lsb_ctx_t* ctx, int rank, int64_t m, const void* queries_dev,
                 int key_type, int flags, int mode, int64_t* out_dev);
 
+/* ---- the matches themselves: value lookup and matched pairs ---------------- */
+/* What lsb_search counts, handed back: for each query the value stored with
+ * its key (lsb_lookup: dictionary decode, a dimension-table fetch, index_of),
+ * and all (query index, record) pairs with equal keys, materialised
+ * (lsb_join_count + lsb_store_join: the sort-merge join whose probe side
+ * lsb_search is).
+ * The preconditions are those of lsb_search: the rank's A is sorted by mapped
+ * key; queries_dev is a column of m typed keys on the rank's device, read with
+ * key_type and flags as lsb_load_columns reads its keys.  Equality is equality
+ * of the mapped key's bits: -0.0 and +0.0 are two keys, a NaN equals only its
+ * own bit pattern, a descending load is searched with LSB_ORDER_DESCENDING.
+ * Unsorted A is the caller's error and is not detected; the results are then
+ * unspecified, but no record outside the rank's here(rank) slots is read and
+ * nothing is written outside the given outputs.
+ * With e_i = lsb_key_encode(queries_dev[i], key_type, flags), for one rank:
+ *   lower_i = the number of the rank's records with key <  e_i
+ *   c_i     = the number of the rank's records with key == e_i
+ * All three calls are local, not collective, and use the streams as
+ * lsb_search does: a call waits for the rank's stream, runs on it and returns
+ * when its outputs are written.  They share lsb_search's table of every 4096th
+ * key, built by whichever of them comes first after a change of A.
+ *
+ * lsb_lookup: one kernel, no plan.  For every i with c_i > 0, vals_dev[i] =
+ * the value of record lower_i, 8 bytes (val_bytes 8) or its low word
+ * (val_bytes 4): the first match in the rank, after a stable sort of an index
+ * load the lowest input index; and found_dev[i] = 1 when found_dev is given.
+ * For every i with c_i == 0 neither element is touched: the caller prefills
+ * its default and zeros.  At least one of vals_dev and found_dev is required;
+ * vals_dev NULL goes with val_bytes 0.  Each thread writes only the elements
+ * of its own query: no atomics.
+ * Across ranks the global array is sorted, so the global first match lies on
+ * the lowest rank that has one: a caller that calls its local ranks from the
+ * last to the first ends up with the global first match in vals_dev (a later
+ * call overwrites an earlier one's element; first to last leaves the last
+ * rank's first match instead).
+ * m == 0 returns LSB_OK and launches nothing; a rank without records touches
+ * nothing.
+ *
+ * lsb_join_count: computes lower_i and c_i for every query and the exclusive
+ * prefix sum off_i of the c_i (off_m = *total), and keeps them as the rank's
+ * join plan in scratch the library owns: no intermediate column is left to the
+ * caller, so nothing the expansion indexes with can be changed from outside.
+ * counts_dev (optional, int64[m]) = c_i, what LSB_SEARCH_COUNT gives.  *total
+ * (may be NULL) = the rank's pairs.  Everything is 64-bit: *total may exceed
+ * 2^32.  Three kernels (count with a sum per 4096 queries, a scan of those
+ * sums by one workgroup, the offsets), none of which waits for another
+ * workgroup, and one 8-byte read of the total.
+ * Scratch: 16 bytes per query plus 8 bytes per 4096 queries, allocated at the
+ * rank's first call, regrown when a later m is larger, freed with the context;
+ * lsb_rank_footprint does not model it, as for the other scratch.  A failed
+ * allocation returns LSB_ERR_NOMEM and leaves the rank without a plan.
+ * Plans are per rank: a new lsb_join_count on a rank replaces that rank's plan
+ * only.  A plan lasts as the table of lsb_search does: until lsb_generate,
+ * lsb_generate_ex, lsb_copy_in, lsb_load_columns, lsb_sort, lsb_pass,
+ * lsb_label_runs or lsb_scan_runs is called; lsb_select and the calls that
+ * only read A keep it.
+ * m == 0 or a rank without records: *total = 0 and a valid plan of zero pairs;
+ * no kernel is launched (counts_dev, when given, is zeroed).
+ *
+ * lsb_store_join: needs the rank's join plan (LSB_ERR_STATE otherwise).  For
+ * output slot o in [0, total): i = the query with off_i <= o < off_{i+1},
+ * j = o - off_i, p = lower_i + j, and
+ *   left_dev[o]  = query_base + i
+ *   right_dev[o] = the value of record p (val_bytes 8) or its low word (4)
+ *   pos_dev[o]   = rank * per + p, the record's global position
+ * Each output is optional, at least one is required; right_dev NULL goes with
+ * val_bytes 0.  cap = the elements every given output holds.  The rank's pairs
+ * come out ordered by query index, then by record position: after a stable
+ * sort of an index load, by left index, then by right input index.
+ * *count (may be NULL) = total; cap < total returns LSB_ERR_INVALID with
+ * *count set and nothing written; total == 0 returns LSB_OK, launches nothing
+ * and does not examine the pointers.  The plan stays valid: a second store,
+ * for instance with other outputs, gives the same pairs.
+ * One kernel, a workgroup per 2048 outputs: it finds the queries whose pairs
+ * meet its outputs by two searches of off, then every output finds its query
+ * among them, so the work per output is logarithmic whatever the skew (one
+ * query with a million matches, the next thousand with none).
+ * The pairs of the ranks are disjoint and their union is the join with the
+ * whole array: that is the whole cross-rank story, as for lsb_search.
+ *
+ * LSB_ERR_INVALID, before anything is launched: null context, bad rank, m < 0
+ * or cap < 0, unknown key type or flag bits, val_bytes not 0, 4 or 8 or
+ * disagreeing with its pointer, no output, a null queries pointer with m > 0,
+ * the pointer checks of lsb_load_columns on every given column (m elements
+ * each; the outputs of lsb_store_join cap elements each), and any two given
+ * columns of one call that share a byte (queries against an output, or two
+ * outputs).  LSB_ERR_STATE: an earlier sort left the context unusable (as
+ * lsb_sort). */
+int  lsb_lookup(lsb_ctx_t* ctx, int rank, int64_t m, const void* queries_dev, int key_type, int flags,
+                void* vals_dev, int val_bytes, uint8_t* found_dev);
+int  lsb_join_count(lsb_ctx_t* ctx, int rank, int64_t m, const void* queries_dev, int key_type, int flags,
+                    int64_t* counts_dev, int64_t* total);
+int  lsb_store_join(lsb_ctx_t* ctx, int rank, int64_t cap, int64_t query_base, int64_t* left_dev,
+                    void* right_dev, int val_bytes, int64_t* pos_dev, int64_t* count);
+
 /* ---- the hot path ------------------------------------------------------- */
 /* == mySort(A, B): all 64/radix_bits passes; result in A.  Asynchronous
  * with respect to the host except for the per-pass count exchange when

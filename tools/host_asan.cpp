@@ -25,7 +25,8 @@
 //     partitions against the stable sort of the whole array; its refusals;
 //     lsb_select / lsb_store_select with a null context and bad arguments;
 //   - lsb_search with a null context, with a bad mode and with every argument
-//     bad: refused before the columns are looked at;
+//     bad: refused before the columns are looked at; lsb_lookup,
+//     lsb_join_count and lsb_store_join alike;
 //   - k_onesweep's tile geometry where passes of different tile sizes meet
 //     (csrc/lsb_ostile.h): the look-back rows' fill decision replayed over
 //     random launch sequences (no launch can read a row of its own parity
@@ -587,6 +588,36 @@ static void search_cases() {
   for (int i = 0; i < 4; ++i) CHECK(out[i] == -5 && q[i] == (uint64_t)i, "search: a refusal writes nothing");
 }
 
+// The refusals of lsb_lookup, lsb_join_count and lsb_store_join that come
+// before any device call.
+static void join_cases() {
+  uint64_t q[4] = {0, 1, 2, 3};
+  int64_t col[3][4];
+  uint8_t found[4] = {0x55, 0x55, 0x55, 0x55};
+  for (auto& c : col)
+    for (int64_t& x : c) x = -5;
+  int64_t total = -5;
+  for (int vb : {0, 4, 8, 3}) {
+    CHECK(lsb_lookup(nullptr, 0, 4, q, LSB_KEY_U64, 0, vb ? col[0] : nullptr, vb, found) == LSB_ERR_INVALID,
+          "lookup: null ctx");
+    CHECK(lsb_store_join(nullptr, 0, 4, 0, col[0], vb ? col[1] : nullptr, vb, col[2], &total) == LSB_ERR_INVALID,
+          "store_join: null ctx");
+  }
+  CHECK(lsb_lookup(nullptr, 0, 0, nullptr, LSB_KEY_U64, 0, nullptr, 0, nullptr) == LSB_ERR_INVALID,
+        "lookup: null ctx, m = 0");
+  CHECK(lsb_lookup(nullptr, -1, -1, nullptr, 6, 2, nullptr, 8, nullptr) == LSB_ERR_INVALID, "lookup: all bad");
+  CHECK(lsb_join_count(nullptr, 0, 4, q, LSB_KEY_U64, 0, col[0], &total) == LSB_ERR_INVALID, "join_count: null ctx");
+  CHECK(lsb_join_count(nullptr, 0, 0, nullptr, LSB_KEY_U64, 0, nullptr, nullptr) == LSB_ERR_INVALID,
+        "join_count: null ctx, m = 0");
+  CHECK(lsb_join_count(nullptr, -1, -1, nullptr, 6, 2, nullptr, &total) == LSB_ERR_INVALID, "join_count: all bad");
+  CHECK(lsb_store_join(nullptr, -1, -1, 7, nullptr, nullptr, 5, nullptr, nullptr) == LSB_ERR_INVALID,
+        "store_join: all bad");
+  for (int i = 0; i < 4; ++i)
+    CHECK(col[0][i] == -5 && col[1][i] == -5 && col[2][i] == -5 && found[i] == 0x55 && q[i] == (uint64_t)i,
+          "join: a refusal writes nothing");
+  CHECK(total == -5, "join: a refusal leaves the total");
+}
+
 static int noop_ag(void*, const void*, void*, size_t) { return 0; }
 static int noop_a2a(void*, const void*, const size_t*, const size_t*, void*, const size_t*,
                     const size_t*) { return 0; }
@@ -773,6 +804,7 @@ int main() {
   runs_cases(rng);
   select_cases(rng);
   search_cases();
+  join_cases();
   onesweep_tile_cases(rng);
   uint64_t col[4] = {0, 1, 2, 3};  // host memory: never reaches a device call with a null context
   CHECK(lsb_load_columns(nullptr, 0, 0, 4, col, LSB_KEY_U64, col, 8, 0) == LSB_ERR_INVALID, "load: null ctx");
