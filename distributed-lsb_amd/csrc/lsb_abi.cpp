@@ -403,6 +403,66 @@ int lsb_store_columns(lsb_ctx_t* c, int rank, int64_t off, int64_t cnt, void* ke
 
 namespace {
 
+// What both rekeys check first.  *rank_out: the rank, once they have passed.
+int check_rekey(lsb_ctx* c, int rank, const char* where, Rank** rank_out) {
+  LSB_TRY(check_ctx(c));
+  if (c->broken)
+    return fail(LSB_ERR_STATE, where, "an earlier sort failed and left packed records in A; load the input again");
+  Rank* r = local_rank(c, rank);
+  if (!r) return fail(LSB_ERR_INVALID, where, "rank");
+  *rank_out = r;
+  return LSB_OK;
+}
+
+// The rekey's error word: the third word of the rank's check scratch, whose
+// other users (lsb_verify, lsb_check_sorted, allreduce_min_i64) take the first.
+uint32_t* rekey_err(Rank& r) { return reinterpret_cast<uint32_t*>(r.check + 2); }
+
+}  // namespace
+
+int lsb_rekey_columns(lsb_ctx_t* c, int rank, const void* keys_dev, int64_t n_col, int key_type, int flags) {
+  const char* where = "lsb_rekey_columns";
+  Rank* r = nullptr;
+  LSB_TRY(check_rekey(c, rank, where, &r));
+  if (!lsb::key_form_valid(key_type, flags)) return fail(LSB_ERR_INVALID, where, "key type or flags");
+  if (n_col <= 0) return fail(LSB_ERR_INVALID, where, "n_col");
+  if (r->here == 0) return LSB_OK;
+  if (!keys_dev) return fail(LSB_ERR_INVALID, where, "null keys");
+  HIP_TRY(hipSetDevice(r->dev));
+  LSB_TRY(check_column(*r, keys_dev, (size_t)lsb::key_bytes(key_type), n_col, where));
+  runs_invalidate(c);
+  select_invalidate(c);
+  search_invalidate(c);
+  HIP_TRY(hipStreamSynchronize(r->stream));
+  uint32_t h = 0;
+  LSB_TRY(guarded_launch(*r, rekey_err(*r), &h, [&]() -> int {
+    HIP_TRY(lsb::launch_rekey_columns(r->A, r->here, keys_dev, n_col, key_type, flags, rekey_err(*r), r->stream));
+    return LSB_OK;
+  }));
+  if (h != 0)
+    return fail(LSB_ERR_INVALID, where,
+                "a record's value is not below n_col; such records are unchanged, the others carry their new keys");
+  return LSB_OK;
+}
+
+int lsb_rekey_index(lsb_ctx_t* c, int rank, uint64_t divisor) {
+  const char* where = "lsb_rekey_index";
+  Rank* r = nullptr;
+  LSB_TRY(check_rekey(c, rank, where, &r));
+  if (divisor == 0) return fail(LSB_ERR_INVALID, where, "divisor 0");
+  if (r->here == 0) return LSB_OK;
+  runs_invalidate(c);
+  select_invalidate(c);
+  search_invalidate(c);
+  HIP_TRY(hipSetDevice(r->dev));
+  HIP_TRY(hipStreamSynchronize(r->stream));
+  HIP_TRY(lsb::launch_rekey_index(r->A, r->here, divisor, r->stream));
+  HIP_TRY(hipStreamSynchronize(r->stream));
+  return LSB_OK;
+}
+
+namespace {
+
 // A sort that failed part-way may leave work queued on a rank's placement
 // or wire stream (an exchange's placements, the chunked exchange's
 // transfers) that reads or writes the record buffers; the next call on the

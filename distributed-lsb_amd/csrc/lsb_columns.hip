@@ -3,9 +3,18 @@
 // and value arrays on the device become the {u64 key, u64 val} records the
 // passes sort, and back.  Keys go through the order-preserving forms of
 // lsb_keyform.h.  Both kernels are pure streams: every byte is read once and
-// written once, nothing else is done.
+// written once, nothing else is done.  k_rekey (lsb_rekey_columns /
+// lsb_rekey_index) is the third: it streams the records in
+// place and gathers each one's new key from a caller's column by its value.
 #include "lsb_kernels.h"
 #include "lsb_keyform.h"
+
+#ifdef LSB_DEBUG
+#include <cassert>
+#define LSB_REKEY_ASSERT(c) assert(c)
+#else
+#define LSB_REKEY_ASSERT(c) ((void)0)
+#endif
 
 namespace lsb {
 
@@ -222,6 +231,97 @@ __global__ __launch_bounds__(256) void k_store_columns(const Elem* __restrict__ 
   }
 }
 
+// Records per thread and iteration of k_rekey (E): the gathers one thread has
+// in flight together.  Measured at 2, 4 and 8: the permuted
+// gather is indifferent, and at 2 a lane's records are 32 adjacent bytes, which
+// streams best (as k_load_columns' E == 2).
+#ifndef LSB_REKEY_GROUP
+#define LSB_REKEY_GROUP 2
+#endif
+constexpr int kRekeyGroup = LSB_REKEY_GROUP;
+
+enum class RekeyBy { kColumn, kIndex };
+
+// x, as a value the compiler knows nothing about.  It keeps the compiler from
+// storing only the half of a record that changed (a value that went through
+// here is no longer known to equal memory), and from sinking a gather under
+// the branch on its bound: that would make the gathers wait for one another.
+__device__ __forceinline__ uint64_t opaque(uint64_t x) {
+  asm volatile("" : "+v"(x));
+  return x;
+}
+
+// N adjacent records at a, rekeyed in place by their values v = a[j].val:
+//   kColumn  key = encode(col[v]); a record with v >= bound (the column's
+//            length, >= 1) keeps its key, and the result is true
+//   kIndex   key = v / bound (the divisor, >= 1); col is not looked at
+// All N records are read, all N bounds decided and all N gathers issued before
+// the first gathered key is used, so a thread's N gathers are in flight
+// together.  An out-of-range record gathers col[0] instead, so no address is
+// ever formed from its value and the body has no branch; it is written back
+// with the key it had.
+template <typename KeyT, RekeyBy By, int N>
+__device__ __forceinline__ bool rekey_records(Elem* __restrict__ a, const KeyT* __restrict__ col, uint64_t bound,
+                                              const KeyForm& form) {
+  Elem e[N];
+  uint64_t k[N];
+  bool bad = false;
+#pragma unroll
+  for (int j = 0; j < N; ++j) e[j] = load_elem(a + j);
+#pragma unroll
+  for (int j = 0; j < N; ++j) e[j].val = opaque(e[j].val);
+  if constexpr (By == RekeyBy::kColumn) {
+    uint64_t at[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) at[j] = e[j].val < bound ? e[j].val : 0;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      LSB_REKEY_ASSERT(at[j] < bound);
+      k[j] = col[at[j]];
+    }
+#pragma unroll
+    for (int j = 0; j < N; ++j) k[j] = opaque(k[j]);  // all N gathers are in flight by now
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      const bool in = e[j].val < bound;
+      bad |= !in;
+      k[j] = in ? encode(k[j], form) : e[j].key;
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < N; ++j) k[j] = e[j].val / bound;
+  }
+#pragma unroll
+  for (int j = 0; j < N; ++j) store_elem(a + j, Elem{k[j], e[j].val});
+  return bad;
+}
+
+// Slots [0, cnt) of A rekeyed in place (rekey_records).  Thread t of the grid
+// takes records [t * E, (t + 1) * E) per iteration, and the cnt % E last
+// records go one per thread; every thread writes back only what it read, and
+// never a value that differs from the one it read.  kColumn: a wave that met
+// an out-of-range value raises *err; kIndex: err is not looked at.
+template <typename KeyT, RekeyBy By>
+__global__ __launch_bounds__(256) void k_rekey(Elem* __restrict__ A, const KeyT* __restrict__ col, int64_t cnt,
+                                               uint64_t bound, int key_type, int flags,
+                                               uint32_t* __restrict__ err) {
+  constexpr int E = kRekeyGroup;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t groups = cnt / E;
+  const KeyForm form = key_form(key_type, flags);
+  bool bad = false;
+  for (int64_t g = tid; g < groups; g += stride) bad |= rekey_records<KeyT, By, E>(A + g * E, col, bound, form);
+  if constexpr (E > 1) {
+    const int64_t i = groups * E + tid;  // the tail: fewer than E records
+    if (i < cnt) bad |= rekey_records<KeyT, By, 1>(A + i, col, bound, form);
+  }
+  if constexpr (By == RekeyBy::kColumn) {
+    // One plain store per wave that met a bad value (every lane gets here).
+    if (__ballot(bad) != 0 && (threadIdx.x & 63) == 0) *err = 1u;
+  }
+}
+
 int grid_for(int64_t work, int block, int cap) {
   const int64_t g = (work + block - 1) / block;
   return (int)(g < 1 ? 1 : (g > cap ? cap : g));
@@ -296,6 +396,29 @@ hipError_t launch_store_columns(const Elem* A, int64_t cnt, void* keys, int key_
     if (k32) store_columns_form<uint32_t, 0>(A, cnt, keys, key_type, vals, flags, s);
     else store_columns_form<uint64_t, 0>(A, cnt, keys, key_type, vals, flags, s);
   }
+  return hipGetLastError();
+}
+
+hipError_t launch_rekey_columns(Elem* A, int64_t cnt, const void* keys, int64_t n_col, int key_type, int flags,
+                                uint32_t* err, hipStream_t s) {
+  if (!key_form_valid(key_type, flags) || !keys || n_col <= 0 || !err) return hipErrorInvalidValue;
+  if (cnt <= 0) return hipSuccess;
+  const dim3 grid(grid_for(cnt / kRekeyGroup, 256, 8192));  // the tail: threads of block 0
+  if (key_bytes(key_type) == 4)
+    hipLaunchKernelGGL((k_rekey<uint32_t, RekeyBy::kColumn>), grid, dim3(256), 0, s, A,
+                       static_cast<const uint32_t*>(keys), cnt, (uint64_t)n_col, key_type, flags, err);
+  else
+    hipLaunchKernelGGL((k_rekey<uint64_t, RekeyBy::kColumn>), grid, dim3(256), 0, s, A,
+                       static_cast<const uint64_t*>(keys), cnt, (uint64_t)n_col, key_type, flags, err);
+  return hipGetLastError();
+}
+
+hipError_t launch_rekey_index(Elem* A, int64_t cnt, uint64_t divisor, hipStream_t s) {
+  if (divisor == 0) return hipErrorInvalidValue;
+  if (cnt <= 0) return hipSuccess;
+  const dim3 grid(grid_for(cnt / kRekeyGroup, 256, 8192));  // the tail: threads of block 0
+  hipLaunchKernelGGL((k_rekey<uint64_t, RekeyBy::kIndex>), grid, dim3(256), 0, s, A,
+                     static_cast<const uint64_t*>(nullptr), cnt, divisor, kKeyU64, 0, static_cast<uint32_t*>(nullptr));
   return hipGetLastError();
 }
 

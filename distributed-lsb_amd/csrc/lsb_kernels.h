@@ -446,6 +446,17 @@ hipError_t launch_load_columns(Elem* A, int64_t cnt, const void* keys, int key_t
                                int val_bytes, uint64_t val0, int flags, hipStream_t s);
 hipError_t launch_store_columns(const Elem* A, int64_t cnt, void* keys, int key_type, void* vals, int val_bytes,
                                 int flags, hipStream_t s);
+// The records A[0, cnt) rekeyed in place by their values (k_rekey, one launch
+// on s).  Columns: A[i].key = encode(keys[A[i].val]) with keys a column of
+// n_col elements of key_type, aligned to its element; a record whose value is
+// not below n_col stays as it is, no address is formed from it, and *err (a
+// device word the caller zeroed) becomes non-zero.  Index: A[i].key =
+// A[i].val / divisor.  The values are never written differently.
+// hipErrorInvalidValue on an unknown key type or flag, null keys or err,
+// n_col <= 0 or divisor == 0, before any launch.
+hipError_t launch_rekey_columns(Elem* A, int64_t cnt, const void* keys, int64_t n_col, int key_type, int flags,
+                                uint32_t* err, hipStream_t s);
+hipError_t launch_rekey_index(Elem* A, int64_t cnt, uint64_t divisor, hipStream_t s);
 hipError_t launch_verify(const Elem* A, int64_t here, int64_t gbase, int64_t n, int64_t per,
                          KeyGen gen, unsigned long long* first_bad, hipStream_t s);
 

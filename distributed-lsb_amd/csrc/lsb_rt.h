@@ -83,7 +83,7 @@ struct Rank {
   int64_t* plan_work = nullptr;         // [P][nb] device-plan scratch
   int64_t* plan_total = nullptr;        // [nb]    device-plan scratch
   int64_t* plan_counts = nullptr;       // [2P] send counts, recv counts
-  unsigned long long* check = nullptr;  // [4] verify / check_sorted scratch
+  unsigned long long* check = nullptr;  // [4] verify / check_sorted scratch; [2]: lsb_rekey_columns' error word
   uint64_t* span = nullptr;             // [2] OR of keys, OR of ~keys (first pass of lsb_sort)
   uint64_t* span_gather = nullptr;      // [2P] all-gathered spans (RCCL)
   uint64_t* span_h = nullptr;           // [2P] pinned host mirror

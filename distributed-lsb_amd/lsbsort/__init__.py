@@ -211,6 +211,8 @@ def _lib() -> ctypes.CDLL:
             "lsb_key_decode": (ctypes.c_uint64, [ctypes.c_uint64, i32, i32]),
             "lsb_load_columns": (i32, [vp, i32, i64, i64, vp, i32, vp, i32, i32]),
             "lsb_store_columns": (i32, [vp, i32, i64, i64, vp, i32, vp, i32, i32]),
+            "lsb_rekey_columns": (i32, [vp, i32, vp, i64, i32, i32]),
+            "lsb_rekey_index": (i32, [vp, i32, ctypes.c_uint64]),
             "lsb_plan_runs": (i32, [i64, i32, vp, vp, vp, vp, vp, P64]),
             "lsb_count_runs": (i32, [vp, P64, vp, vp]),
             "lsb_store_runs": (i32, [vp, i32, i64, vp, i32, i32, vp, vp, vp, i32, P64]),
@@ -260,7 +262,8 @@ def _lib() -> ctypes.CDLL:
             # An older build given through LSB_LIBRARY (A/B timing against the
             # parent commit) lacks the newest entry points; calling them there raises.
             if name in ("lsb_get_last_packed_tile", "lsb_get_last_pass_tiles", "lsb_search", "lsb_lookup",
-                        "lsb_join_count", "lsb_store_join") and not hasattr(L, name):
+                        "lsb_join_count", "lsb_store_join", "lsb_rekey_columns", "lsb_rekey_index") \
+                    and not hasattr(L, name):
                 continue
             fn = getattr(L, name)
             fn.restype = res
@@ -416,6 +419,190 @@ def sort(keys, values=None, descending: bool = False, ranks: int = 1, radix_bits
         for r, lo, h in blocks:
             w.store_columns(r, out_k[lo:lo + h], out_v[lo:lo + h], descending=descending, key_type=kt)
     return out_k, out_v
+
+
+def _check_sort_columns(columns, descending):
+    """sort_by's arguments -> (columns, key types, one descending flag per
+    column).  ValueError on anything sort_by refuses."""
+    import torch
+    if isinstance(columns, torch.Tensor) or not isinstance(columns, (list, tuple)):
+        raise ValueError("columns: not a sequence of 1-D tensors")
+    cols = list(columns)
+    if not cols:
+        raise ValueError("columns: empty")
+    for i, c in enumerate(cols):
+        if not isinstance(c, torch.Tensor) or c.dim() != 1:
+            raise ValueError(f"columns[{i}]: not a 1-D torch tensor")
+    if any(c.numel() != cols[0].numel() for c in cols):
+        raise ValueError("columns differ in length")
+    if any(c.device != cols[0].device for c in cols):
+        raise ValueError("columns on different devices")
+    if isinstance(descending, (bool, np.bool_)):
+        desc = [bool(descending)] * len(cols)
+    else:
+        desc = [bool(d) for d in descending]
+        if len(desc) != len(cols):
+            raise ValueError("descending: one flag per column")
+    for i, c in enumerate(cols):
+        _check_column(c, f"columns[{i}]")
+    return cols, [_key_type_of(c) for c in cols], desc
+
+
+def _sort_world_by(w, cols, kts, desc) -> list:
+    """The LSD sort over columns in w (n = the columns' length): the last
+    column loaded with index values and sorted, then every earlier column,
+    last to first, rekeyed into the records and sorted again.  -> the
+    non-empty ranks' (rank, first index, records)."""
+    blocks = [(r, r * w.per, w.here(r)) for r in range(w.P) if w.here(r)]
+    for r, lo, h in blocks:
+        w.load_columns(r, cols[-1][lo:lo + h], None, descending=desc[-1], key_type=kts[-1])
+    w.my_sort()
+    for c, kt, d in reversed(list(zip(cols[:-1], kts[:-1], desc[:-1]))):
+        for r, _, _ in blocks:
+            w.rekey(r, c, descending=d, key_type=kt)
+        w.my_sort()
+    return blocks
+
+
+def sort_by(columns, descending=False, ranks: int = 1, radix_bits: int = 8):
+    """The stable lexicographic argsort of device columns: int64 indices i
+    such that (columns[0][i], columns[1][i], ...) ascends, columns[0] the
+    primary (ORDER BY a, b, c; numpy.lexsort with the columns reversed).
+
+    columns: one or more 1-D contiguous CUDA tensors of equal length on one
+    device, any mix of sort()'s key dtypes; descending: one bool, or one per
+    column.  Rows equal on every column keep their input order.  Float order
+    and equality (of bits) are those of lsb.h.  With one column the result is
+    sort(x)[1].  The inputs are left untouched.  One World(n, ranks) on the
+    columns' device sorts by the last column, then rekeys by and sorts on each
+    earlier one; every rank reads the whole columns."""
+    import torch
+    cols, kts, desc = _check_sort_columns(columns, descending)
+    if ranks < 1:
+        raise ValueError("ranks")
+    n = cols[0].numel()
+    out = torch.empty(n, dtype=torch.int64, device=cols[0].device)
+    if n == 0:
+        return out
+    dev = cols[0].device.index if cols[0].device.index is not None else torch.cuda.current_device()
+    with World(n, ranks=ranks, devices=[dev] * ranks, radix_bits=radix_bits) as w:
+        for r, lo, h in _sort_world_by(w, cols, kts, desc):
+            w.store_columns(r, None, out[lo:lo + h])
+    return out
+
+
+def sort_rows(keys2d, descending: bool = False, ranks: int = 1, radix_bits: int = 8):
+    """Every row of a 2-D tensor sorted stably: (sorted_keys, indices), both
+    [R, L], indices int64 within the row (torch.sort(stable=True, dim=-1)).
+
+    keys2d: a contiguous 2-D CUDA tensor of one of sort()'s key dtypes, left
+    untouched.  One World(R * L, ranks) sorts the flattened keys with index
+    values, rekeys every record by its row (index // L) and sorts again: the
+    second sort runs only the passes the row numbers need."""
+    import torch
+    if not isinstance(keys2d, torch.Tensor) or keys2d.dim() != 2:
+        raise ValueError("keys2d: not a 2-D torch tensor")
+    if not keys2d.is_cuda:
+        raise ValueError("keys2d: not on a GPU")
+    if not keys2d.is_contiguous():
+        raise ValueError("keys2d: not contiguous")
+    flat = keys2d.reshape(-1)
+    _check_column(flat, "keys2d")
+    kt = _key_type_of(flat)
+    if ranks < 1:
+        raise ValueError("ranks")
+    R, L = keys2d.shape
+    n = R * L
+    v = torch.empty(n, dtype=torch.int64, device=keys2d.device)
+    if n == 0:
+        return torch.empty_like(keys2d), v.reshape(R, L)
+    dev = keys2d.device.index if keys2d.device.index is not None else torch.cuda.current_device()
+    with World(n, ranks=ranks, devices=[dev] * ranks, radix_bits=radix_bits) as w:
+        blocks = [(r, r * w.per, w.here(r)) for r in range(ranks) if w.here(r)]
+        for r, lo, h in blocks:
+            w.load_columns(r, flat[lo:lo + h], None, descending=descending, key_type=kt)
+        w.my_sort()
+        for r, _, _ in blocks:
+            w.rekey_index(r, L)
+        w.my_sort()
+        for r, lo, h in blocks:
+            w.store_columns(r, None, v[lo:lo + h])
+    return flat[v].reshape(R, L), (v % L).reshape(R, L)
+
+
+def segment_sort(keys, offsets, descending: bool = False, ranks: int = 1, radix_bits: int = 8):
+    """Keys sorted stably inside caller-given segments (CSR rows, ragged
+    batches): (sorted_keys, indices), indices the int64 global input indices.
+
+    keys: as for sort(); offsets: int64 tensor of S + 1 non-decreasing offsets
+    from 0 to len(keys), segment s being keys[offsets[s]:offsets[s + 1]]
+    (empty segments allowed).  The segment ids are built with torch, then it
+    is sort_by([segment_ids, keys]).  The inputs are left untouched."""
+    import torch
+    if not isinstance(keys, torch.Tensor) or keys.dim() != 1:
+        raise ValueError("keys: not a 1-D torch tensor")
+    if not isinstance(offsets, torch.Tensor) or offsets.dim() != 1 or offsets.dtype != torch.int64:
+        raise ValueError("offsets: not a 1-D int64 torch tensor")
+    n = keys.numel()
+    if offsets.numel() < 1 or int(offsets[0]) != 0 or int(offsets[-1]) != n:
+        raise ValueError("offsets: not from 0 to len(keys)")
+    if offsets.numel() > 1 and int((offsets[1:] - offsets[:-1]).min()) < 0:
+        raise ValueError("offsets: decreasing")
+    _check_column(keys, "keys")
+    _key_type_of(keys)
+    if ranks < 1:
+        raise ValueError("ranks")
+    off = offsets.to(keys.device)
+    counts = off[1:] - off[:-1]
+    if n == 0:
+        return torch.empty_like(keys), torch.empty(0, dtype=torch.int64, device=keys.device)
+    S = counts.numel()
+    ids = torch.repeat_interleave(torch.arange(S, dtype=torch.int64, device=keys.device), counts)
+    if S <= 1 << 31:  # a 32-bit primary column: its upper digits are skipped
+        ids = ids.to(torch.int32)
+    idx = sort_by([ids, keys], [False, descending], ranks=ranks, radix_bits=radix_bits)
+    return keys[idx], idx
+
+
+def group_quantile(keys, values, q: float = 0.5, descending: bool = False, ranks: int = 1, radix_bits: int = 8):
+    """One order statistic per group of equal keys: (unique_keys,
+    quantile_values), the first answer here to PARTITION BY key ORDER BY value.
+
+    unique_keys: the distinct keys in sorted order (descending: reversed), as
+    unique(); quantile_values[j]: of the group's values sorted ascending in the
+    value dtype's key order, the element at position floor(q * (count - 1))
+    (float64 arithmetic): q = 0 the minimum, 0.5 the lower median, 1 the
+    maximum.  keys and values: as sort()'s keys, equal length, one device.
+    The inputs are left untouched.  One World(n, ranks) sorts by [keys,
+    values], counts the runs and stores their keys, starts and counts; one
+    gather picks the values."""
+    import torch
+    if not (isinstance(q, (int, float)) and 0.0 <= float(q) <= 1.0):
+        raise ValueError("q: not in [0, 1]")
+    cols, kts, _ = _check_sort_columns([keys, values], False)
+    if ranks < 1:
+        raise ValueError("ranks")
+    n = keys.numel()
+    if n == 0:
+        return torch.empty_like(keys), torch.empty_like(values)
+    dev = keys.device.index if keys.device.index is not None else torch.cuda.current_device()
+    with World(n, ranks=ranks, devices=[dev] * ranks, radix_bits=radix_bits) as w:
+        blocks = _sort_world_by(w, cols, kts, [descending, False])
+        idx = torch.empty(n, dtype=torch.int64, device=keys.device)
+        for r, lo, h in blocks:
+            w.store_columns(r, None, idx[lo:lo + h])
+        plan = w.count_runs()
+        total = plan["total"]
+        out_k = torch.empty(total, dtype=keys.dtype, device=keys.device)
+        starts = torch.empty(total, dtype=torch.int64, device=keys.device)
+        counts = torch.empty(total, dtype=torch.int64, device=keys.device)
+        for r in range(ranks):
+            lo, m = plan["bases"][r], plan["runs"][r]
+            if m:
+                w.store_runs(r, keys=out_k[lo:lo + m], starts=starts[lo:lo + m], counts=counts[lo:lo + m],
+                             descending=descending, key_type=kts[0])
+    pos = starts + torch.floor(float(q) * (counts - 1).to(torch.float64)).to(torch.int64)
+    return out_k, values[idx[pos]]
 
 
 def _store_inverse(w, inverse) -> None:
@@ -1166,6 +1353,30 @@ class World:
         _check(_lib().lsb_store_columns(self._h, rank, off, cols[0].numel(),
                                         None if keys is None else keys.data_ptr(), kt, vp, vb,
                                         ORDER_DESCENDING if descending else 0), "lsb_store_columns")
+
+    def rekey(self, rank: int, column, descending: bool = False, key_type: Optional[int] = None) -> None:
+        """lsb_rekey_columns: every record of `rank` gets the key of
+        column[its value], in place; the values stay.  column: the WHOLE
+        column (a 1-D contiguous CUDA torch tensor on the rank's device, dtype
+        and key_type= as for load_columns), since the values are global input
+        indices.  A value that is no index into it fails with LSB_ERR_INVALID
+        and leaves that record as it was.  torch's current stream is
+        synchronized first; the call returns when the records are rekeyed."""
+        import torch
+        _check_column(column, "column")
+        kt = _key_type_of(column, key_type)
+        torch.cuda.current_stream(column.device).synchronize()
+        _check(_lib().lsb_rekey_columns(self._h, rank, column.data_ptr() if column.numel() else None,
+                                        column.numel(), kt, ORDER_DESCENDING if descending else 0),
+               "lsb_rekey_columns")
+
+    def rekey_index(self, rank: int, divisor: int = 1) -> None:
+        """lsb_rekey_index: every record of `rank` gets the key value //
+        divisor, in place (1: the input index itself; L: the row of a
+        row-major [R, L] array)."""
+        if not 0 <= divisor < 1 << 64:
+            raise ValueError("divisor")
+        _check(_lib().lsb_rekey_index(self._h, rank, divisor), "lsb_rekey_index")
 
     def count_runs(self) -> dict:
         """lsb_count_runs: the runs of equal keys of the whole array (a

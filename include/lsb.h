@@ -325,6 +325,53 @@ int  lsb_store_columns(lsb_ctx_t* ctx, int rank, int64_t off, int64_t cnt,
                        void* keys_dev, int key_type,
                        void* vals_dev, int val_bytes, int flags);
 
+/* ---- ordering by several columns: rekey by a gathered column --------------- */
+/* A sorted array whose values are input indices is a permutation.  The rekey
+ * replaces each record's key with the key of that input row in another
+ * column, so that the next (stable) lsb_sort orders by that column and keeps
+ * the order reached so far among its equal keys: an LSD sort over columns,
+ * least significant column first (ORDER BY a, b, c; numpy.lexsort).
+ *
+ * lsb_rekey_columns: for every slot i in [0, here(rank)) of local rank
+ * `rank`, with v = A[i].val (all 64 bits, unsigned), the record becomes
+ * {lsb_key_encode(keys_dev[v], key_type, flags), v}.  keys_dev is a column of
+ * n_col typed keys on the rank's device, read as lsb_load_columns reads its
+ * keys (all six key types, LSB_ORDER_DESCENDING).  The value is not changed.
+ * The rekey is in place: A and B do not swap, slots [here, per) are not
+ * touched, and each thread rewrites only the records it read.
+ * In a world of several ranks the values are global input indices, so every
+ * rank needs the WHOLE column (all n_col = n keys) on its own device, not its
+ * block of it; worlds whose columns are not replicated are out of scope.
+ *
+ * lsb_rekey_index: the record becomes {v / divisor, v} (unsigned division),
+ * no column involved.  divisor 1 restores "key = input index", so a following
+ * lsb_sort returns the records to input order; divisor L keys each record by
+ * its row of a row-major [R, L] array (sort by key, rekey by row, sort again:
+ * every row sorted).
+ *
+ * Both calls are local, not collective, and work alike in every kind of
+ * context.  here(rank) == 0 returns LSB_OK, launches nothing and does not
+ * look at keys_dev.  Streams as lsb_load_columns: the call waits for the
+ * rank's own stream, runs one kernel on it and returns once it has finished.
+ * Both change the records, so they end the run plan, the select plan, the
+ * search table and the join plan as lsb_load_columns does.
+ * LSB_ERR_INVALID, before any kernel is launched and with A untouched: null
+ * context or bad rank; unknown key type or flag bits; null keys_dev;
+ * n_col <= 0; the pointer checks of lsb_load_columns on keys_dev over n_col
+ * elements; divisor == 0.  LSB_ERR_STATE as lsb_sort, when an earlier failed
+ * sort left the context unusable.
+ * LSB_ERR_INVALID after the kernel, from lsb_rekey_columns, when some
+ * record's value is >= n_col.  The kernel forms no address from such a value
+ * and leaves that record as it was.  Afterwards every value and every slot is
+ * intact; the keys of the records whose values are in range have already been
+ * replaced.  The caller still holds its columns and the indices are still in
+ * the records, so it can rekey again (with the right column, or with
+ * lsb_rekey_index).  The error word is 8 bytes of scratch every rank has from
+ * its creation. */
+int  lsb_rekey_columns(lsb_ctx_t* ctx, int rank, const void* keys_dev, int64_t n_col,
+                       int key_type, int flags);
+int  lsb_rekey_index(lsb_ctx_t* ctx, int rank, uint64_t divisor);
+
 /* ---- runs of equal keys --------------------------------------------------- */
 /* What a caller does next with a sorted array: the distinct keys, how often
  * each occurs, where each group starts and which input record was its first
@@ -361,8 +408,9 @@ int  lsb_store_columns(lsb_ctx_t* ctx, int rank, int64_t off, int64_t cnt,
  * every rank of the world.  n == 0: *total = 0, nothing is launched.  The
  * first call allocates 12 bytes per 4096 records of scratch on each rank.
  * The plan stays valid until lsb_generate, lsb_generate_ex, lsb_copy_in,
- * lsb_load_columns, lsb_sort, lsb_pass, lsb_label_runs or lsb_scan_runs is called.  In a one-rank-per-
- * process world lsb_copy_in and lsb_load_columns are local calls and drop the
+ * lsb_load_columns, lsb_rekey_columns, lsb_rekey_index, lsb_sort, lsb_pass,
+ * lsb_label_runs or lsb_scan_runs is called.  In a one-rank-per-process world
+ * lsb_copy_in, lsb_load_columns and the two rekeys are local calls and drop the
  * plan of the calling process only, while the other ranks' plans depend on
  * its records (a run's count reaches into later ranks): after any rank has
  * changed its records, every rank calls lsb_count_runs again before its next
@@ -667,7 +715,8 @@ int  lsb_scan_runs(lsb_ctx_t* ctx, int mode);
  * and bases[P] as lsb_plan_select gives them for count = k + 1, for every
  * rank of the world.  Every output may be NULL.
  * The context keeps the plan (pivot and the per-rank counts) until
- * lsb_generate, lsb_generate_ex, lsb_copy_in, lsb_load_columns, lsb_sort,
+ * lsb_generate, lsb_generate_ex, lsb_copy_in, lsb_load_columns,
+ * lsb_rekey_columns, lsb_rekey_index, lsb_sort,
  * lsb_pass, lsb_label_runs or lsb_scan_runs is called: the calls that end a run plan, and
  * the note on one-rank-per-process worlds there applies unchanged.  The run
  * plan and the reduce plan are left alone, and lsb_count_runs,
@@ -760,7 +809,8 @@ int  lsb_get_last_select(lsb_ctx_t* ctx, int* rounds, int64_t* records_read);
  * 4096th record into a table (8 bytes per 4096 records of scratch, allocated
  * at the rank's first search and freed with the context; lsb_rank_footprint
  * does not model it, as for the other scratch).  The table is kept until
- * lsb_generate, lsb_generate_ex, lsb_copy_in, lsb_load_columns, lsb_sort,
+ * lsb_generate, lsb_generate_ex, lsb_copy_in, lsb_load_columns,
+ * lsb_rekey_columns, lsb_rekey_index, lsb_sort,
  * lsb_pass, lsb_label_runs or lsb_scan_runs is called.  lsb_select leaves A
  * bit for bit and uses B only, so it keeps the table; so do the calls that
  * only read A.  A query then costs a binary search of that table and at most
@@ -835,7 +885,8 @@ int  lsb_search(lsb_ctx_t* ctx, int rank, int64_t m, const void* queries_dev,
  * allocation returns LSB_ERR_NOMEM and leaves the rank without a plan.
  * Plans are per rank: a new lsb_join_count on a rank replaces that rank's plan
  * only.  A plan lasts as the table of lsb_search does: until lsb_generate,
- * lsb_generate_ex, lsb_copy_in, lsb_load_columns, lsb_sort, lsb_pass,
+ * lsb_generate_ex, lsb_copy_in, lsb_load_columns, lsb_rekey_columns,
+ * lsb_rekey_index, lsb_sort, lsb_pass,
  * lsb_label_runs or lsb_scan_runs is called; lsb_select and the calls that
  * only read A keep it.
  * m == 0 or a rank without records: *total = 0 and a valid plan of zero pairs;
