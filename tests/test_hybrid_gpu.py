@@ -16,6 +16,7 @@ kept input with the LSD passes (without trusting the fused pass's output).
 import numpy as np
 import pytest
 
+import hybrid_model as hm
 from test_gpu_sort import DT, _dist
 
 pytestmark = pytest.mark.gpu
@@ -125,6 +126,8 @@ def test_long_runs_take_the_segment_sort(lsb_built, oracle_mod):
     out, (lp, _, _), _ = _sort(lsb_built, a)
     assert np.array_equal(out, oracle_mod.stable_sort(a))
     assert lp == 3 + 1  # 3 byte passes + the segmented sort
+    model = hm.hybrid_sort(a, 1)  # the CPU model of the same input: k_segfix's bit 1 alone
+    assert (model.route, lp) == ("segsort", model.passes)
 
 
 @pytest.mark.parametrize("n", [1 << 23, (1 << 23) + 4_097])
@@ -155,6 +158,8 @@ def test_crossing_runs_past_one_window(lsb_built, oracle_mod, mids, run):
     out, (lp, _, _), _ = _sort(lsb_built, a)
     assert np.array_equal(out, oracle_mod.stable_sort(a))
     assert lp == 3  # 3 byte passes, segments merged by k_segfix
+    model = hm.hybrid_sort(a, 1)  # the CPU model of the same input: no error bit
+    assert (model.route, lp) == ("fused", model.passes)
 
 
 @pytest.mark.parametrize("bases", [1024, 4096, 1 << 15])
@@ -174,9 +179,13 @@ def test_long_segments_fall_back_to_lsd(lsb_built, oracle_mod, bases):
     # 3 byte passes, then (the fused pass found a segment past kSegMax inside
     # a tile: its output is no permutation) straight to the 8 LSD passes
     assert lp == 3 + 8
+    model = hm.hybrid_sort(a, 1)  # the CPU model of the same input: bit 2
+    assert (model.route, lp) == ("lsd", model.passes)
     out, (lp, _, _), _ = _sort(lsb_built, a, mode=2)
     assert np.array_equal(out, oracle_mod.stable_sort(a))
     assert lp == 3 + 1 + 8  # mode 2: the byte passes, the failed k_segsort, the LSD passes
+    model = hm.hybrid_sort(a, 2)
+    assert (model.route, lp) == ("lsd", model.passes)
 
 
 def _stress_seed19_iter3258(n):
