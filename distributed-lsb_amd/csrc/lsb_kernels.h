@@ -146,8 +146,9 @@ hipError_t launch_subhist(const Elem* A, int64_t m, int shift, int grid, uint32_
 // next_hist (zeroed here) = sub_hist of the digit at next_shift over out.
 // tile_ctr: kOnesweepSubs words of scratch; *err |= 1 if a look-back gave up.
 // -DLSB_OS_PROFILE builds: summed s_memtime ticks of k_onesweep's phases
-// (dequeue, load + rank, look-back + scan, stage, write, unused) over all
-// workgroups' thread 0; hipErrorNotSupported otherwise.
+// (0 dequeue, 1 load + rank, 2 publish + scan, 3 stage, 4 write, 5 look-back,
+// 6 tile loads in flight, 9 run cuts + the barrier after them; 7 rows summed,
+// 8 tiles) over all workgroups' thread 0; hipErrorNotSupported otherwise.
 hipError_t onesweep_profile(unsigned long long* out10, bool reset);
 // What a pass also hands the exchange that follows it (per-digit exchange
 // forms, P > 1): totals[b] = the pass's 256 digit counts; count16 (zeroed

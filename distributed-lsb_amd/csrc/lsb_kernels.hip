@@ -992,6 +992,11 @@ constexpr int kSegWin = LSB_SEG_WIN;
 #ifndef LSB_GATHER_PF
 #define LSB_GATHER_PF 64
 #endif
+// A bucket's run cuts from a plan made once per sub-array (os_cut_plan,
+// lsb_ostile.h) instead of os_run_cut per tile (0: per tile, for A/B runs).
+#ifndef LSB_OS_CUTPLAN
+#define LSB_OS_CUTPLAN 1
+#endif
 
 // SEG (the hybrid's last pass, SegPass in lsb_kernels.h): the write-out also
 // orders each segment (records equal on seg.pmask; inside the tile they are
@@ -1136,13 +1141,17 @@ __device__ __forceinline__ void onesweep_body(
     for (int i = t; i < kSub * kBuckets; i += BLOCK) nh[i] = 0;
 
 #ifdef LSB_OS_PROFILE
-  uint64_t prof[10] = {};  // phases 0-6; 7: rows summed in look-backs, 8: tiles
+  uint64_t prof[10] = {};  // phases 0-6 and 9; 7: rows summed in look-backs, 8: tiles
   uint64_t prof_last = __builtin_amdgcn_s_memtime();
 #endif
   int sub = (int)(blockIdx.x % kSub);  // thread 0's dequeue cursor
   int tries = 0;
   int cur_sub = -1;
   uint64_t base = 0;  // bstart + sub_pre[cur_sub][t]
+  // Bucket t's cut plan in sub-array cur_sub: its output range there against
+  // the next pass's sub-array boundaries (RG = 1: a constant, below).
+  constexpr bool kPlan = LSB_OS_CUTPLAN && NEXT && RG != 1;
+  OsCutWords plan = {0u, 0u};
   // Thread 0: the next tile of sub-array `sub` in order, else of the next
   // sub-array (-1 when all are taken).
   auto grab = [&](int& tile_out, int& sub_out) {
@@ -1209,10 +1218,15 @@ __device__ __forceinline__ void onesweep_body(
         base = (uint64_t)region_base((bkt ? t : 0) * kSub + x, rg.cap);  // region (t, x)
       } else {
         uint64_t pre = 0;
+        uint32_t len = 0;  // sub_hist[x][t]
 #pragma unroll
-        for (int xx = 0; xx < kSub; ++xx)
-          pre += xx < x ? (kCol ? col[xx] : (bkt ? sub_hist[xx * kBuckets + t] : 0u)) : 0u;
+        for (int xx = 0; xx < kSub; ++xx) {
+          const uint32_t v = xx <= x ? (kCol ? col[xx] : (bkt ? sub_hist[xx * kBuckets + t] : 0u)) : 0u;
+          pre += xx < x ? v : 0u;
+          len = xx == x ? v : len;
+        }
         base = bstart + pre;
+        if (kPlan) plan = os_cut_words(os_cut_plan((int64_t)base, len, TN, TTn, mcap), (int64_t)base, len);
       }
       cur_sub = x;
     }
@@ -1501,6 +1515,7 @@ __device__ __forceinline__ void onesweep_body(
       __builtin_amdgcn_raw_buffer_store_b64(v2u{(ea + cnt) | tag_pre, (eb + cnt_b) | tag_pre}, rs,
                                             my_off, 0, kStPol);
     }
+    OS_MARK(5);  // look-back
     const uint32_t eb_left = pair_swap(eb);  // odd lanes: lane t - 1's sum
     const uint64_t excl = even ? ea : eb_left;
     int64_t R = (int64_t)(base + excl);  // first output slot of the run
@@ -1522,12 +1537,15 @@ __device__ __forceinline__ void onesweep_body(
         // sub-arrays are 256 whole regions): no run crosses one.
         c = 0xFFFFu | ((uint32_t)(t >> 5) << 16) | ((uint32_t)(t >> 5) << 24);
       } else if (cnt > 0) {
-        c = os_run_cut(R, cnt, lstart, TN, TTn, mcap);
+        // One boundary at the most lies in the bucket's range of this
+        // sub-array, but for a bucket that covers a whole next-pass sub-array.
+        if (kPlan && !(plan.xs & kOsCutGeneral)) c = os_cut(plan, (uint32_t)excl, cnt, lstart);
+        else c = os_run_cut(R, cnt, lstart, TN, TTn, mcap);
       }
       cut[t] = c;
     }
     __syncthreads();
-    OS_MARK(5);  // look-back (+ run cuts, barrier)
+    OS_MARK(9);  // run cuts, barrier
 #ifdef LSB_OS_PROFILE
     if (t == 0) ++prof[8];
 #endif

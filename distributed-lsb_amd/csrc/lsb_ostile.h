@@ -46,6 +46,62 @@ LSB_HD inline uint32_t os_run_cut(int64_t R, uint32_t cnt, uint32_t lstart, int 
   return 0xFFFFu | ((uint32_t)x0 << 16) | ((uint32_t)x0 << 24);
 }
 
+// os_run_cut's answer hardly depends on the tile: bucket t's runs of one
+// sub-array of this pass all lie in the output slots [base, base + len), len
+// being the bucket's count in that sub-array, and the next pass's seven
+// boundaries fall inside few such ranges.  The plan of a range, made once
+// when a workgroup enters the sub-array: x0, the next-pass sub-array of slot
+// `base`; bnd, the first next-pass boundary above `base` (mcap past the last
+// one); x1, the sub-array that starts at bnd; general: the range goes on past
+// a second boundary (a bucket that covers a whole next-pass sub-array), and
+// its runs keep calling os_run_cut.
+struct OsCutPlan {
+  int64_t bnd;
+  int x0, x1;
+  bool general;
+};
+LSB_HD inline OsCutPlan os_cut_plan(int64_t base, int64_t len, int tn, int64_t TTn, int64_t mcap) {
+  OsCutPlan p;
+  p.x0 = os_sub_of_tile(base / tn, TTn);
+  p.bnd = p.x0 + 1 < kOnesweepSubs ? os_sub_first_tile(p.x0 + 1, TTn) * tn : mcap;
+  p.x1 = os_sub_of_tile(p.bnd / tn, TTn);
+  const int64_t bnd2 = p.x1 + 1 < kOnesweepSubs ? os_sub_first_tile(p.x1 + 1, TTn) * tn : mcap;
+  p.general = base + len > bnd2;
+  return p;
+}
+// os_run_cut's word for a run [R, R + cnt) of a range whose plan is not
+// general: two compares of R against the one boundary.
+LSB_HD inline uint32_t os_cut(const OsCutPlan& p, int64_t R, uint32_t cnt, uint32_t lstart) {
+  const uint32_t x0 = (uint32_t)p.x0, x1 = (uint32_t)p.x1;
+  if (R + cnt <= p.bnd) return 0xFFFFu | (x0 << 16) | (x0 << 24);
+  if (R >= p.bnd) return 0xFFFFu | (x1 << 16) | (x1 << 24);
+  return (uint32_t)(lstart + (p.bnd - R)) | (x0 << 16) | (x1 << 24);
+}
+// The plan as the two words a bucket thread keeps: the boundary relative to
+// `base` (a run starts at base + excl with excl + cnt <= len < 2^32, so 32
+// bits hold it whatever m is) and x0 << 16 | x1 << 24 | general.  A range
+// that ends at or before the boundary takes x1 = x0 and rel = 0: every run
+// is then "past the boundary", all in x0.
+struct OsCutWords {
+  uint32_t rel, xs;
+};
+constexpr uint32_t kOsCutGeneral = 1u;
+LSB_HD inline OsCutWords os_cut_words(const OsCutPlan& p, int64_t base, uint32_t len) {
+  const bool reach = p.bnd - base < (int64_t)len;  // some run may start, or end, past bnd
+  const uint32_t x0 = (uint32_t)p.x0, x1 = reach ? (uint32_t)p.x1 : x0;
+  OsCutWords w;
+  w.rel = reach ? (uint32_t)(p.bnd - base) : 0u;
+  w.xs = (x0 << 16) | (x1 << 24) | (p.general ? kOsCutGeneral : 0u);
+  return w;
+}
+// os_cut from the words: the run starts excl slots into the range.
+LSB_HD inline uint32_t os_cut(const OsCutWords& w, uint32_t excl, uint32_t cnt, uint32_t lstart) {
+  const uint32_t hi = w.xs & 0xFF000000u, lo = w.xs & 0x00FF0000u;
+  if (excl >= w.rel) return 0xFFFFu | (hi >> 8) | hi;
+  if (w.rel - excl >= cnt) return 0xFFFFu | lo | (lo << 8);
+  return (lstart + (w.rel - excl)) | lo | hi;
+}
+
 // A run of at most t records may cross at most one boundary of the next
 // pass's sub-arrays, so every non-empty sub-array that a run can cover whole
 // and go on past must hold at least t records.  A non-empty sub-array holds
